@@ -6,17 +6,27 @@ Metric: GiB/s device-resident LZ4 compress+decompress of 1M x 16 KiB pages
 compress pass + one decompress pass over the rank's 1,048,576 resident pages;
 value = uncompressed bytes of all ranks' pages x steps / max-over-ranks wall time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C4] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 --config C4 measures BASELINE configs[3] instead: LZ4 decompress-only of 8M x 8 KiB
 pages, split over the ranks by contiguous page ranges (strong scaling).
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP events on
-the codec's stream) and `cpu_baseline` (the reference's vendored LZ4 1.7.5 from
-oracle/_ref, timed by oracle/_ref/cpu_baseline: C pthreads on every core the
-process may use -- its affinity mask, capped by its cgroup CPU quota -- over a
-bounded sample of the same pages).
+the codec's stream, taken in the timed steps themselves).  A plain run does only
+that: set up, warm up, time the steps, check the last step's round trip, print.
+
+--dump-outputs DIR writes what the last timed step returned to its caller as
+DIR/<name>.npy (float32; see dump_outputs).  The pages depend only on the
+arguments, so two builds can be compared output for output.
+
+--full adds the measurements that take runs of their own, on one GPU:
+`e2e_host_path` (the PCIe-inclusive host batch API and a link probe),
+`cpu_baseline` (the reference's vendored LZ4 1.7.5 from oracle/_ref, timed by
+oracle/_ref/cpu_baseline: C pthreads on every core the process may use -- its
+affinity mask, capped by its cgroup CPU quota -- over a bounded sample of the
+same pages) and `configs` (C3 zstd and the C4 shard).  --no-cpu, --e2e-pages 0
+and --no-extra drop single legs of it.
 """
 from __future__ import annotations
 
@@ -50,16 +60,26 @@ def parse():
     ap.add_argument("--seed", type=int, default=20170303)
     ap.add_argument("--cpu-pages", type=int, default=131072, help="CPU baseline sample (pages, at least 2048 per thread)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core the process may use (affinity, cgroup quota)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--e2e-pages", type=int, default=32768, help="host-buffer (PCIe-inclusive) sample; 0 = skip")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary C3 (zstd) measurement")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--e2e-pages", type=int, default=32768,
+                    help="with --full: host-buffer (PCIe-inclusive) sample; 0 = skip")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the secondary C3 (zstd) and C4-shard measurements")
     ap.add_argument("--extra-pages", type=int, default=1 << 20, help="pages for the C3 zstd measurement")
     ap.add_argument("--extra-steps", type=int, default=2)
     ap.add_argument("--config", default="C2", choices=["C2", "C4"],
                     help="C2: the headline (LZ4 compress+decompress, 1M x 16 KiB per GPU); "
                          "C4: BASELINE configs[3], LZ4 decompress-only of 8M x 8 KiB pages split over the ranks")
     ap.add_argument("--c4-pages", type=int, default=8 << 20, help="C4 total pages over all ranks")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (host path and link probe, CPU baseline, C3 zstd, "
+                         "C4 shard); a plain run times the headline steps only")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_cpu() -> tuple[int, str]:
@@ -117,6 +137,51 @@ def pages_equal(out, pages, rv, plen: int) -> bool:
     for a in range(0, out.shape[0], step):
         ok = ok and torch.equal(out[a:a + step], pages[a:a + step])
     return ok
+
+
+DUMP_SAMPLE_PAGES = 256            # whole pages (and their compressed slots) kept by --dump-outputs
+DUMP_SAMPLE_BYTES = 44_000_000     # cap of those samples as float32; with the per-page results (at most
+DUMP_MAX_RESULTS = 2 << 20         # 2M values = 8 MB per file) a dump stays under 64 MB
+
+
+def dump_outputs(path: str, seed: int, out, rv, comp=None, clen=None) -> dict:
+    """--dump-outputs: what the last timed step returned to its caller, as float32 .npy files in `path`
+    (u8 bytes and page lengths are exact in float32).  Runs after the timed region.
+
+      rv.npy          decompress_pages' result per page (the decoded length, or an error code)
+      out_sample.npy  the decoded bytes of a fixed sample of pages, [k, page_len]
+      clen.npy        compress_pages' result per page (the stream's length)          -- with `comp`
+      comp_sample.npy the same pages' streams, [k, slot], zero past each stream's end -- with `comp`
+
+    The page sample is DUMP_SAMPLE_PAGES page numbers drawn without replacement by
+    numpy.random.default_rng(seed), sorted, fewer where pages are large; the per-page results are
+    complete up to DUMP_MAX_RESULTS pages and the same kind of sample beyond."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n, plen = out.shape
+    width = plen + (comp.shape[1] if comp is not None else 0)
+    rng = np.random.default_rng(seed)
+    k = max(1, min(n, DUMP_SAMPLE_PAGES, DUMP_SAMPLE_BYTES // (4 * width)))
+    idx = torch.from_numpy(np.sort(rng.choice(n, size=k, replace=False))).to(out.device)
+    arrays = {"out_sample": out.index_select(0, idx)}
+    if n > DUMP_MAX_RESULTS:
+        ridx = torch.from_numpy(np.sort(rng.choice(n, size=DUMP_MAX_RESULTS, replace=False))).to(out.device)
+        arrays["rv"] = rv.index_select(0, ridx)
+    else:
+        ridx = None
+        arrays["rv"] = rv
+    if comp is not None:
+        arrays["clen"] = clen if ridx is None else clen.index_select(0, ridx)
+        lens = clen.index_select(0, idx)
+        cols = torch.arange(comp.shape[1], device=comp.device)
+        arrays["comp_sample"] = comp.index_select(0, idx) * (cols[None, :] < lens[:, None])
+    written = {}
+    for name, t in arrays.items():
+        a = t.cpu().numpy().astype(np.float32)
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def measure_codec(cid: int, name: str, n: int, plen: int, steps: int, warmup: int, dev, seed: int, first: int,
@@ -340,6 +405,9 @@ def run_c4(args, info, dev):
     elapsed = runner.max_over_ranks(info, time.perf_counter() - t0)
     if not pages_equal(out, pages, rv, plen):   # the last timed step's output, after the timed region
         raise SystemExit("C4: round trip failed")
+    dumped = None
+    if args.dump_outputs and info.rank == 0:
+        dumped = dump_outputs(args.dump_outputs, args.seed, out, rv)
     del pages
     comp_bytes = int(clen.to(torch.int64).sum().item())
     d_ms = sum(e[0].elapsed_time(e[1]) for e in events) / args.steps
@@ -364,6 +432,8 @@ def run_c4(args, info, dev):
                      "algorithmic_bytes_per_launch": algo},
         "kernel_ms": {"lz4_decode": round(d_ms, 4)}, "ratio": round(n * plen / comp_bytes, 4),
     }
+    if dumped is not None:
+        result["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if info.rank == 0:
         print(json.dumps(result), flush=True)
     runner.shutdown(info)
@@ -428,6 +498,9 @@ def main():
     if not (bool((clen > 0).all().item()) and pages_equal(out, pages, rv, plen)):
         raise SystemExit("round trip failed on the benchmark pages")
     comp_bytes = int(clen.to(torch.int64).sum().item())
+    dumped = None
+    if args.dump_outputs and info.rank == 0:
+        dumped = dump_outputs(args.dump_outputs, args.seed, out, rv, comp, clen)
 
     c_ms = sum(e[0].elapsed_time(e[1]) for e in events) / args.steps
     d_ms = sum(e[1].elapsed_time(e[2]) for e in events) / args.steps
@@ -470,7 +543,9 @@ def main():
         "roofline_by_kernel": {k: round(algo_bytes / (v * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) for k, v in kernels.items()},
         "ratio": round(page_bytes / comp_bytes, 4),
     }
-    if info.rank == 0 and info.world == 1:
+    if dumped is not None:
+        result["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if args.full and info.rank == 0 and info.world == 1:
         threads = args.cpu_threads or host_cpu()[0]
         if args.e2e_pages > 0:
             result["e2e_host_path"] = e2e_host(pages, min(args.e2e_pages, n))
