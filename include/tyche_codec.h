@@ -200,6 +200,15 @@ size_t tyche_plan_split(size_t n, const uint32_t *src_lengths, int ndev, uint64_
  * in-process override; for tests and A/B timing.  No knob changes a decode
  * result; encoder-shape knobs (LZ4_ENC_WAVES, ZSTD_PARSE_WAVES, ZSTD_FSE_LOG)
  * change the compressed bytes and ratio, never whether they decode to the page.
+ * A fourth, LZ4_EXACT (default 0), sends every LZ4 compress launch (pages of up
+ * to 65535 bytes, every entry point) to the exact encoder: results[i] and the
+ * bytes are those of LZ4 1.7.5's LZ4_compress_default(src, dst, src_len,
+ * dst_capacity), including its 0 when a capacity below LZ4_compressBound fails
+ * one of its conservative checks, and nothing at or past dst + dst_capacity is
+ * written.  src_len == 0 gives the one-byte block 0x00 (result 1; 0 when
+ * dst_capacity is 0), as the default encoder does; a page above the launch's
+ * maximum still gives INT32_MIN.  It changes the bytes and the time (about 14x
+ * the default encoder's), never the decode result.
  * Two are test hooks: FAIL_COMPRESS_EVERY=N fails every Nth compress launch
  * (TYCHE_E_DEVICE, the device-failure test) and LOG_ERRORS=1 prints engine
  * errors to stderr. */

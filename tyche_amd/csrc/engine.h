@@ -78,6 +78,8 @@ hipError_t launch_lz4_decode_quad(const tyche_batch_t &b, uint32_t in_cap, uint3
 // large batches, round 4: one page per lane, chunked, aligned LDS (lz4_decode_lc.hip)
 hipError_t launch_lz4_decode_lc(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
 hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
+// LZ4_EXACT=1: the bytes and return value of LZ4 1.7.5's LZ4_compress_default (lz4_encode_exact.hip)
+hipError_t launch_lz4_encode_exact(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);

@@ -963,6 +963,8 @@ __global__ __launch_bounds__(64) void lz4_encode_kernel(tyche_batch_t b, uint32_
 hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
     if (b.count == 0) return hipSuccess;
     if (in_cap > 65535u) return hipErrorInvalidValue;    // 16-bit positions (byU16 regime)
+    // TYCHE_LZ4_EXACT=1: every launch to the exact encoder (LZ4 1.7.5's bytes, lz4_encode_exact.hip)
+    if (knob("LZ4_EXACT", 0) != 0) return launch_lz4_encode_exact(b, in_cap, s);
     // TYCHE_LZ4_ENC=1: the one-wave kernel for every batch (A/B timing)
     const bool one_wave = knob("LZ4_ENC", 0) == 1;
     // waves per page of the split encoders (2: the two-wave kernel; 3 in round 3: 79.4 vs 85.0 ms per
