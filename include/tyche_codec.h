@@ -137,7 +137,29 @@ int tyche_restore_queue_hist(uint64_t *counts, int n);
  *                      or a negative value wherever ZSTD_isError holds.
  *   INT32_MIN marks a page larger than the launch's declared maximum.
  * max_src_length (0 = unknown) bounds src lengths for LDS sizing.
+ *
+ * Page sizes.  LZ4 takes pages, and decodes into capacities, of up to
+ * TYCHE_LZ4_MAX_PAGE bytes (streams up to tyche_compress_bound of that) at
+ * every entry point, host and device, for any batch size: a compress batch
+ * declares its maximum (src_length, or max_src_length beside src_lengths; 0
+ * there keeps meaning "at most 65535"), and a declared maximum or a host page
+ * above the limit is TYCHE_E_BAD_ARGS with the limit in tyche_last_error(); a
+ * decode capacity above it is refused at the launch (TYCHE_E_DEVICE), as every
+ * capacity beyond the decoders' reach always was.  tyche_decompress_host also
+ * refuses (TYCHE_E_DEVICE, at the chunk that holds the first large page, the
+ * rule in tyche_last_error()) a bulk batch that mixes the classes: one holding
+ * a capacity above 65536 bytes beside more than 64 pages of at most that.  The
+ * rule looks at the batch alone.  Such batches were always refused this way,
+ * and a staging chunk is launched whole, so the small pages would share the
+ * one-page-per-CU decoders of the large ones.  Pass large pages in calls of
+ * their own; the Buffer entry points and the restore queue do so themselves.
+ * A page above 65535 bytes still becomes one standard LZ4 block; in a batch that
+ * mixes sizes, the pages of up to 65535 bytes get the bytes they would get
+ * without the larger ones.  zlib and zstd compress pages of up to 65535 bytes
+ * only (TYCHE_E_BAD_ARGS above), and so does LZ4 under LZ4_EXACT=1 (below).
  * `stream` is a hipStream_t (NULL = default stream); the call is asynchronous. */
+#define TYCHE_LZ4_MAX_PAGE (4u << 20)   /* largest LZ4 page length and decode capacity */
+
 typedef struct tyche_batch {
     size_t count;
     const void *src;
@@ -208,7 +230,10 @@ size_t tyche_plan_split(size_t n, const uint32_t *src_lengths, int ndev, uint64_
  * written.  src_len == 0 gives the one-byte block 0x00 (result 1; 0 when
  * dst_capacity is 0), as the default encoder does; a page above the launch's
  * maximum still gives INT32_MIN.  It changes the bytes and the time (about 14x
- * the default encoder's), never the decode result.
+ * the default encoder's), never the decode result.  It is a promise about the
+ * reference's byU16 regime only: with the knob on, an LZ4 compress launch whose
+ * declared maximum (or a host page) exceeds 65535 bytes fails with
+ * TYCHE_E_BAD_ARGS instead of being given another encoder's bytes.
  * Two are test hooks: FAIL_COMPRESS_EVERY=N fails every Nth compress launch
  * (TYCHE_E_DEVICE, the device-failure test) and LOG_ERRORS=1 prints engine
  * errors to stderr. */

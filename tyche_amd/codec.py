@@ -8,6 +8,12 @@ Layout in HBM: pages are rows of a (n, page_len) uint8
 tensor; compressed pages are rows of a (n, slot) uint8 tensor whose slot is
 ``compress_bound(page_len)`` rounded up to 128 bytes, plus an int32 length per
 row.  Only ``comp_len`` bytes of a slot are read or written by the kernels.
+
+Page sizes: LZ4 rows may be up to ``TYCHE_LZ4_MAX_PAGE`` (4 MiB) long, in both
+directions; rows above 65,535 bytes take the large-page kernels and still
+become one standard LZ4 block each.  zlib and zstd compress rows of up to
+65,535 bytes, and so does LZ4 under ``LZ4_EXACT=1``; beyond a limit the call
+raises ``DeviceError`` (``TYCHE_E_BAD_ARGS``, the limit in the message).
 """
 from __future__ import annotations
 
@@ -50,7 +56,8 @@ def compress_pages(pages: torch.Tensor, compressor_id: int = LZ4_COMPRESSOR_ID, 
     """Compress every row of ``pages``; returns (slots, comp_len).
 
     comp_len[i] is LZ4_compress_default's return for row i (compressed bytes,
-    0 on failure).  Asynchronous on the current stream.
+    0 on failure).  Asynchronous on the current stream.  LZ4 rows may be up to
+    4 MiB long (module docstring).
     """
     _check_pages(pages, "pages")
     n, page_len = pages.shape
@@ -74,6 +81,7 @@ def decompress_pages(slots: torch.Tensor, comp_len: torch.Tensor, page_len: int,
 
     rv[i] is LZ4_decompress_safe's return (decoded size, or -(consumed)-1).
     ``max_comp_len`` (optional) bounds comp_len for LDS sizing; 0 = slot width.
+    LZ4: page_len up to 4 MiB, whoever wrote the blocks.
     """
     _check_pages(slots, "slots")
     if comp_len.dtype != torch.int32 or not comp_len.is_cuda:
@@ -108,6 +116,9 @@ def decompress_ragged(stream: torch.Tensor, offsets: torch.Tensor, lengths: torc
 def compress_ragged(src: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, out: torch.Tensor,
                     out_offsets: torch.Tensor, capacities: torch.Tensor, results: torch.Tensor, max_src_length: int,
                     compressor_id: int = LZ4_COMPRESSOR_ID, level: int = 1):
+    """General form of compress_pages.  ``max_src_length`` declares the longest page (0: at most
+    65,535 bytes); a longer page gets INT32_MIN.  With LZ4 it may be up to 4 MiB, and in a batch
+    that mixes sizes the pages of up to 65,535 bytes get the bytes they would get on their own."""
     b = _lib.Batch(count=offsets.numel(), src=_ptr(src), src_offsets=_ptr(offsets), src_lengths=_ptr(lengths),
                    max_src_length=max_src_length, dst=_ptr(out), dst_offsets=_ptr(out_offsets),
                    dst_capacities=_ptr(capacities), results=_ptr(results))

@@ -80,6 +80,11 @@ hipError_t launch_lz4_decode_lc(const tyche_batch_t &b, uint32_t in_cap, uint32_
 hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 // LZ4_EXACT=1: the bytes and return value of LZ4 1.7.5's LZ4_compress_default (lz4_encode_exact.hip)
 hipError_t launch_lz4_encode_exact(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
+// pages above 65,535 bytes, up to TYCHE_LZ4_MAX_PAGE (lz4_encode_large.hip): the pages of at least min_len
+// bytes; the results of shorter ones are left alone
+hipError_t launch_lz4_encode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t min_len, hipStream_t s);
+// launches beyond the LDS of the other decoders, up to TYCHE_LZ4_MAX_PAGE (lz4_decode_large.hip)
+hipError_t launch_lz4_decode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
 hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);

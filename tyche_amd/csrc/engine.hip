@@ -493,6 +493,24 @@ hipError_t launch_encode(int id, const tyche_batch_t &b, uint32_t in_cap, hipStr
     if (id == TYCHE_ZLIB_COMPRESSOR_ID) return launch_zlib_deflate(b, in_cap, s);
     return launch_lz4_encode(b, in_cap, s);
 }
+// The largest page a compress launch may declare (and a host page may have): TYCHE_LZ4_MAX_PAGE
+// for LZ4, whose large-page encoder takes over above 65,535 bytes; 65,535 for zlib and zstd
+// (16-bit positions in their parses) and for LZ4 under LZ4_EXACT=1, which promises the reference's
+// byU16 bytes and is never quietly given another encoder's.
+int check_page_limit(int id, uint32_t len) {
+    if (len <= 65535u) return TYCHE_E_OK;
+    if (id == TYCHE_LZ4_COMPRESSOR_ID) {
+        if (knob("LZ4_EXACT", 0) != 0) {
+            t_error = "LZ4_EXACT=1 covers pages of up to 65535 bytes only (the reference's byU16 regime)";
+            return TYCHE_E_BAD_ARGS;
+        }
+        if (len <= TYCHE_LZ4_MAX_PAGE) return TYCHE_E_OK;
+        t_error = "LZ4 pages above TYCHE_LZ4_MAX_PAGE (" + std::to_string(TYCHE_LZ4_MAX_PAGE) + " bytes) are not supported";
+        return TYCHE_E_BAD_ARGS;
+    }
+    t_error = std::string(id == TYCHE_ZSTD_COMPRESSOR_ID ? "zstd" : "zlib") + " pages above 65535 bytes are not supported";
+    return TYCHE_E_BAD_ARGS;
+}
 bool valid_decode_codec(int id) {
     return id == TYCHE_LZ4_COMPRESSOR_ID || id == TYCHE_ZLIB_COMPRESSOR_ID || id == TYCHE_ZSTD_COMPRESSOR_ID;
 }
@@ -561,6 +579,7 @@ struct Arena {
 
 constexpr int kSlots = 4;   // round 3: 4 x 32 MiB (was 3 x 64 MiB): the host path waited on streams ~30 % of a call
 constexpr size_t kChunkBytes = size_t(32) << 20;
+constexpr size_t kBulkSmallMax = 64;   // pages of up to 65,536 bytes a raw LZ4 host decode batch may hold beside larger ones
 constexpr int kContextsPerDevice = 8;
 
 struct Slot {
@@ -1380,7 +1399,7 @@ int tyche_compress_batch(int compressor_id, int compressor_level, const tyche_ba
     if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
     uint32_t in_cap = batch->src_lengths ? batch->max_src_length : batch->src_length;
     if (batch->src_lengths && in_cap == 0) in_cap = 65535;
-    if (in_cap > 65535) { t_error = "pages above 64 KiB are not supported by the device encoders"; return TYCHE_E_BAD_ARGS; }
+    if (int rc = check_page_limit(compressor_id, in_cap)) return rc;
     DeviceGuard keep;
     if (int rc = stream_device((hipStream_t)stream)) return rc;
     hipError_t e = launch_encode(compressor_id, *batch, in_cap, (hipStream_t)stream);
@@ -1407,7 +1426,13 @@ int tyche_decompress_batch(int compressor_id, const tyche_batch_t *batch, void *
         if (e != hipSuccess) return fail("zstd decode launch", e);
         return TYCHE_E_OK;
     }
-    hipError_t e = launch_lz4_decode(*batch, decode_in_cap(*batch, lz4_bound(out_cap)), out_cap, (hipStream_t)stream);
+    // (a declared stream maximum is only a bound -- a slot width, say: above the longest stream a
+    // capacity of TYCHE_LZ4_MAX_PAGE can have it is taken as that, and a page whose stream is
+    // longer still gets INT32_MIN)
+    const uint32_t lz4_in_cap = std::min(decode_in_cap(*batch, lz4_bound(out_cap)), lz4_bound(TYCHE_LZ4_MAX_PAGE));
+    hipError_t e = launch_lz4_decode(*batch, lz4_in_cap, out_cap, (hipStream_t)stream);
+    if (e != hipSuccess && out_cap > TYCHE_LZ4_MAX_PAGE)
+        return fail("lz4 decode launch (capacities above TYCHE_LZ4_MAX_PAGE, 4194304 bytes, are not supported)", e);
     if (e != hipSuccess) return fail("lz4 decode launch", e);
     return TYCHE_E_OK;
 }
@@ -1419,8 +1444,9 @@ int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const
     (void)compressor_level;
     if (!valid_codec(compressor_id)) { t_error = codec_msg(compressor_id); return TYCHE_E_BAD_ARGS; }
     if (n == 0) return TYCHE_E_OK;
-    for (size_t i = 0; i < n; i++)
-        if (src_lengths[i] > 65535u) { t_error = "pages above 64 KiB are not supported by the device encoders"; return TYCHE_E_BAD_ARGS; }
+    uint32_t longest = 0;
+    for (size_t i = 0; i < n; i++) longest = std::max(longest, src_lengths[i]);
+    if (int rc = check_page_limit(compressor_id, longest)) return rc;
     // LZ4's encoders only store to their destination (never read it back), so their streams may go
     // straight into the pinned staging arena (HOST_DIRECT_OUT=0: stage through HBM and D2H instead)
     const int direct = compressor_id == TYCHE_LZ4_COMPRESSOR_ID && knob("HOST_DIRECT_OUT", 1) ? kDirectAlways : kDirectNone;
@@ -1444,10 +1470,27 @@ int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, c
                               [](const tyche_batch_t &b, hipStream_t s, bool) {
                                   return launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
                               }, true);
-    return run_host(n, src, src_lengths, dst, dst_capacities, results,
-                          [](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
+    // A capacity above TYCHE_LZ4_MAX_PAGE is refused by the launch of the chunk that holds it, as
+    // every capacity beyond the decoders' LDS used to be: TYCHE_E_DEVICE, earlier chunks drained.
+    // So is, at the chunk that holds its first large page, a bulk batch that mixes classes: one that
+    // holds a capacity above 65,536 bytes beside more than kBulkSmallMax pages of at most that.  It
+    // depends on the batch alone, not on where the chunks are cut.  Such batches were always refused
+    // this way (tests/test_host_engine.py pins it with 12,000 small pages and one 1 MiB capacity),
+    // and a chunk is launched whole, so the small pages would share the one-page-per-CU decoders
+    // of the large ones.  The Buffer entry points and the restore queue split the classes
+    // themselves (tyche_buffers_decompress); a few small pages beside large ones pass.
+    size_t n_small = 0, n_large = 0;
+    for (size_t i = 0; i < n; i++) (dst_capacities[i] <= 65536u ? n_small : n_large)++;
+    const bool mixed_bulk = n_large > 0 && n_small > kBulkSmallMax;
+    const int rc = run_host(n, src, src_lengths, dst, dst_capacities, results,
+                          [mixed_bulk](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
+                              if (mixed_bulk && b.dst_capacity > 65536u) return hipErrorInvalidValue;
                               return launch_lz4_decode(b, b.max_src_length, b.dst_capacity, s, !host_dst);
                           }, true, knob("HOST_DIRECT_OUT", 1) ? kDirectLz4Decode : kDirectNone);
+    if (rc == TYCHE_E_DEVICE && mixed_bulk)
+        t_error += " (an LZ4 host batch with a capacity above 65536 bytes beside more than " + std::to_string(kBulkSmallMax) +
+                   " pages of at most that is refused: pass the large pages in a call of their own)";
+    return rc;
 }
 
 // ------------------------------------------------------- Buffer entry points
@@ -1622,6 +1665,14 @@ int tyche_buffers_decompress(Buffer **bufs, int *status, size_t n, int compresso
     }
     if (idx.empty()) return TYCHE_E_OK;
     const size_t m = idx.size();
+    // LZ4: the buffers of up to 65,536 bytes first, the larger ones after them, each class in a host
+    // batch of its own -- the small pages keep their decoders whatever shares the call (or the
+    // restore queue's batch) with them, and only the large ones take the ring decoder
+    size_t n_small = m;
+    if (compressor_id == TYCHE_LZ4_COMPRESSOR_ID)
+        n_small = (size_t)(std::stable_partition(idx.begin(), idx.end(),
+                                                 [&](size_t i) { return bufs[i]->data_length <= 65536u; }) -
+                           idx.begin());
     std::vector<const void *> src(m);
     std::vector<void *> dst(m);
     std::vector<uint32_t> slen(m), dcap(m);
@@ -1638,28 +1689,35 @@ int tyche_buffers_decompress(Buffer **bufs, int *status, size_t n, int compresso
             return TYCHE_E_NO_MEMORY;
         }
     }
-    uint64_t t0 = now_ns();
-    int rc = tyche_decompress_host(compressor_id, m, src.data(), slen.data(), dst.data(), dcap.data(), res.data());
-    uint64_t per = (now_ns() - t0) / m;
-    for (size_t k = 0; k < m; k++) {
-        Buffer *b = bufs[idx[k]];
-        size_t i = idx[k];
-        // LZ4 accepts any rv >= 0 (buffer.c:251-253); zlib needs Z_OK and the exact length (:257-260);
-        // zstd only !ZSTD_isError (:264-266)
-        const bool bad = res[k] < 0 || (compressor_id == TYCHE_ZLIB_COMPRESSOR_ID && (uint32_t)res[k] != b->data_length);
-        if (rc != TYCHE_E_OK || bad) {
-            free(dst[k]);                           // the reference leaks here
-            status[i] = rc != TYCHE_E_OK ? TYCHE_E_DEVICE : TYCHE_E_BUFFER_COMPRESSION_PROBLEM;
-            continue;
+    int rc_all = TYCHE_E_OK;
+    for (int cls = 0; cls < 2; cls++) {
+        const size_t k0 = cls ? n_small : 0, k1 = cls ? m : n_small;
+        if (k0 == k1) continue;
+        uint64_t t0 = now_ns();
+        int rc = tyche_decompress_host(compressor_id, k1 - k0, src.data() + k0, slen.data() + k0, dst.data() + k0,
+                                       dcap.data() + k0, res.data() + k0);
+        uint64_t per = (now_ns() - t0) / (k1 - k0);
+        if (rc != TYCHE_E_OK && rc_all == TYCHE_E_OK) rc_all = rc;
+        for (size_t k = k0; k < k1; k++) {
+            Buffer *b = bufs[idx[k]];
+            size_t i = idx[k];
+            // LZ4 accepts any rv >= 0 (buffer.c:251-253); zlib needs Z_OK and the exact length (:257-260);
+            // zstd only !ZSTD_isError (:264-266)
+            const bool bad = res[k] < 0 || (compressor_id == TYCHE_ZLIB_COMPRESSOR_ID && (uint32_t)res[k] != b->data_length);
+            if (rc != TYCHE_E_OK || bad) {
+                free(dst[k]);                           // the reference leaks here
+                status[i] = rc != TYCHE_E_OK ? TYCHE_E_DEVICE : TYCHE_E_BUFFER_COMPRESSION_PROBLEM;
+                continue;
+            }
+            free(b->data);
+            b->data = dst[k];
+            b->comp_hits++;
+            b->comp_length = 0;
+            b->comp_cost += (uint32_t)per;
+            status[i] = TYCHE_E_OK;
         }
-        free(b->data);
-        b->data = dst[k];
-        b->comp_hits++;
-        b->comp_length = 0;
-        b->comp_cost += (uint32_t)per;
-        status[i] = TYCHE_E_OK;
     }
-    return rc;
+    return rc_all;
 }
 
 int buffer__compress(Buffer *buf, void **compressed_data, int compressor_id, int compressor_level) {

@@ -1878,14 +1878,19 @@ hipError_t launch_lz4_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t o
 #endif
     const size_t lds = off_in + ((in_cap + 16u + kPad + 15u) & ~15u) + TYCHE_LDS_EXTRA;   // EXTRA: occupancy experiments
     if (lds > 160 * 1024) {
-        // large pages: sequential decoder, LDS = page window + stream only
+        // large pages: sequential decoder, LDS = page window + stream only (it holds the whole window and
+        // walks it with 32-bit positions, so capacities above 65,536 bytes that fit here are safe with it)
         const size_t lds2 = ((out_cap + 15u) & ~15u) + ((in_cap + 16u + kPad + 15u) & ~15u);
-        if (lds2 > 160 * 1024) return hipErrorInvalidValue;
+        if (lds2 > 160 * 1024) return launch_lz4_decode_large(b, in_cap, out_cap, s);   // ring decoder, up to 4 MiB
         (void)prepare_launch((const void *)lz4_decode_serial_kernel);
         hipLaunchKernelGGL(lz4_decode_serial_kernel, dim3((unsigned)b.count), dim3(kWave), lds2, s, b, in_cap,
                            out_cap);
         return hipGetLastError();
     }
+    // The wave decoder below packs a match's destination into 16 bits (decode_page: d | off << 16),
+    // so a window above 65,536 bytes that still fits its LDS (pages up to roughly 80 KiB) came back
+    // with wrong bytes and a right size: those launches take the ring decoder too.
+    if (out_cap > 65536u) return launch_lz4_decode_large(b, in_cap, out_cap, s);
     const size_t ncu = prepare_launch((const void *)lz4_decode_wave_kernel);
     // LDS is granted in 512-byte granules per workgroup
     auto lds_for = [&](uint32_t cap) -> size_t {

@@ -962,7 +962,19 @@ __global__ __launch_bounds__(64) void lz4_encode_kernel(tyche_batch_t b, uint32_
 
 hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
     if (b.count == 0) return hipSuccess;
-    if (in_cap > 65535u) return hipErrorInvalidValue;    // 16-bit positions (byU16 regime)
+    if (in_cap > 65535u) {
+        // The kernels below hold 16-bit positions (byU16 regime); longer pages take the large-page
+        // encoder (lz4_encode_large.hip), up to TYCHE_LZ4_MAX_PAGE.  LZ4_EXACT=1 stays a byU16
+        // promise: such a launch fails rather than get another encoder's bytes.
+        if (in_cap > TYCHE_LZ4_MAX_PAGE || knob("LZ4_EXACT", 0) != 0) return hipErrorInvalidValue;
+        // per-page lengths: the pages up to 65,535 bytes first, by today's path and with today's
+        // bytes (it leaves INT32_MIN for the longer ones), then the longer ones
+        if (b.src_lengths) {
+            const hipError_t e = launch_lz4_encode(b, 65535u, s);
+            if (e != hipSuccess) return e;
+        }
+        return launch_lz4_encode_large(b, in_cap, b.src_lengths ? 65536u : 0u, s);
+    }
     // TYCHE_LZ4_EXACT=1: every launch to the exact encoder (LZ4 1.7.5's bytes, lz4_encode_exact.hip)
     if (knob("LZ4_EXACT", 0) != 0) return launch_lz4_encode_exact(b, in_cap, s);
     // TYCHE_LZ4_ENC=1: the one-wave kernel for every batch (A/B timing)
