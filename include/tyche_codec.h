@@ -182,6 +182,70 @@ int tyche_decompress_batch(int compressor_id, const tyche_batch_t *batch, void *
  * compressBound (zlib compress.c:74-78) or ZSTD_compressBound (zstd_compress.c:37) */
 uint32_t tyche_compress_bound(int compressor_id, uint32_t n);
 
+/* ---- LZ4 with a shared dictionary ----------------------------------------- */
+/* The engine compresses every page on its own; a dictionary is a common prefix
+ * that a page's matches may reach into (LZ4_loadDict + LZ4_compress_fast_continue
+ * / LZ4_decompress_safe_usingDict, lz4.c:936, 987, 1382).
+ *
+ * The window.  A dictionary of D bytes followed by a page of L bytes is one LZ4
+ * window.  The compressed page is a standard LZ4 block whose offsets may reach
+ * back as far as the first dictionary byte (offset <= position + D): exactly what
+ * LZ4_decompress_safe_usingDict(stream, dst, n, L, dict, D) restores.  The
+ * end-of-block rules are unchanged.  Compress results are the size, or 0 when the
+ * stream does not fit the capacity; decompress results are
+ * LZ4_decompress_safe_usingDict's value (the decoded size, or -(input bytes
+ * consumed)-1 at the same point of a malformed stream; an offset of exactly
+ * position + D is legal, one more is the error; offset 0 is treated as the plain
+ * decoders treat it: the size is defined, the copied bytes are not).  INT32_MIN
+ * marks a page above the launch's declared maximum, as in tyche_*_batch.  The
+ * encoder matches against the dictionary's last D & ~63 bytes; the decoder honours
+ * all D.  tyche_compress_bound is unchanged.
+ *
+ * Reach.  The dictionary applies to a page when L + D <= 65536 (window positions
+ * fit 16 bits).  Device-resident calls: a compress launch whose declared maximum
+ * (src_length, or max_src_length beside src_lengths; 0 there still means 65535)
+ * plus D exceeds 65536, and a decompress launch whose dst_capacity plus D does, is
+ * TYCHE_E_BAD_ARGS with the rule and both numbers in tyche_last_error().  Host
+ * entry points with a process-wide dictionary (tyche_lz4_use_dict, or
+ * TYCHE_LZ4_DICT below) apply the rule per page -- compress to src_lengths[i],
+ * decompress to dst_capacities[i]; for Buffers both are data_length, so the two
+ * directions always agree.  A page outside the reach takes the path, and gets the
+ * bytes, it has without a dictionary (pages above 65535 bytes included); a batch
+ * that mixes the classes runs as two launches over the same batch.  One
+ * consequence: a raw tyche_decompress_host caller must pass the page length as the
+ * capacity, as Buffers do, or a dictionary stream may land on a plain decoder and
+ * get its error verdict -- a failed restore, never wrong bytes.  Pages written
+ * with a dictionary need the same dictionary to be restored.
+ *
+ * Without a dictionary (tyche_lz4_use_dict never called or given NULL, no
+ * TYCHE_LZ4_DICT, and the plain tyche_*_batch calls) nothing changes: the kernels
+ * launched, the bytes and the results are the same.  LZ4_EXACT=1 and a dictionary
+ * do not combine: a compress call that has both is TYCHE_E_BAD_ARGS.  zlib and
+ * zstd ignore all of this.
+ *
+ * TYCHE_LZ4_DICT=<file> in the environment: the file's bytes become the
+ * process-wide dictionary at the first LZ4 host-path call.  A file that is
+ * unreadable, empty or longer than TYCHE_LZ4_DICT_MAX makes every LZ4 host call
+ * fail with TYCHE_E_BAD_ARGS and the reason; it is never silently ignored.  A
+ * tyche_lz4_use_dict call replaces whatever the variable named.
+ *
+ * Lifetime and threads.  A handle is immutable after creation; the engine uploads
+ * it once per device, lazily and under a lock.  tyche_lz4_dict_destroy drops the
+ * caller's reference; a handle installed process-wide, or used by a launch still
+ * in flight, lives until that use ends. */
+#define TYCHE_LZ4_DICT_MAX 32768u
+typedef struct tyche_lz4_dict tyche_lz4_dict_t;
+/* host bytes, copied; 1..TYCHE_LZ4_DICT_MAX bytes, else NULL with the rule in tyche_last_error() */
+tyche_lz4_dict_t *tyche_lz4_dict_create(const void *bytes, uint32_t len);
+void tyche_lz4_dict_destroy(tyche_lz4_dict_t *d);
+uint32_t tyche_lz4_dict_length(const tyche_lz4_dict_t *d);
+/* device-resident batches, same tyche_batch_t and result rules as tyche_*_batch */
+int tyche_lz4_compress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream);
+int tyche_lz4_decompress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream);
+/* process-wide dictionary of the host entry points (Buffer API, tyche_buffers_*, host batches,
+ * restore queue, multi-device fan-out); NULL removes it.  Holds a reference of its own. */
+int tyche_lz4_use_dict(const tyche_lz4_dict_t *d);
+
 /* ---- host batch API (pinned staging + H2D -> kernels -> D2H) ------------- */
 /* Same per-page semantics as the device batch, with host pointers.  Used by
  * the Buffer entry points and by the PCIe-inclusive measurement. */

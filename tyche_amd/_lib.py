@@ -34,6 +34,7 @@ E_DEVICE = 199
 ALL_DEVICES = -1        # tyche_set_device: spread host work over the device set (TYCHE_ALL_DEVICES)
 
 RESULT_TOO_LARGE = -(2 ** 31)
+LZ4_DICT_MAX = 32768    # TYCHE_LZ4_DICT_MAX
 
 # buffer flags, src/buffer.h:23-33
 FLAG_COMPRESSING = 1 << 5
@@ -107,6 +108,12 @@ SIGNATURES = {
     "tyche_compress_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Batch), ctypes.c_void_p]),
     "tyche_decompress_batch": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Batch), ctypes.c_void_p]),
     "tyche_compress_bound": (ctypes.c_uint32, [ctypes.c_int, ctypes.c_uint32]),
+    "tyche_lz4_dict_create": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_uint32]),
+    "tyche_lz4_dict_destroy": (None, [ctypes.c_void_p]),
+    "tyche_lz4_dict_length": (ctypes.c_uint32, [ctypes.c_void_p]),
+    "tyche_lz4_compress_batch_dict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Batch), ctypes.c_void_p]),
+    "tyche_lz4_decompress_batch_dict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Batch), ctypes.c_void_p]),
+    "tyche_lz4_use_dict": (ctypes.c_int, [ctypes.c_void_p]),
     "tyche_compress_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, _vpp, _u32p, _vpp, _u32p,
                                            _i32p]),
     "tyche_decompress_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _vpp, _u32p, _vpp, _u32p, _i32p]),

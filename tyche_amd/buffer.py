@@ -88,6 +88,14 @@ def buffers_decompress(bufs, compressor_id: int):
     return rc, list(st)
 
 
+def use_dict(dictionary) -> None:
+    """Installs ``dictionary`` (a codec.Lz4Dict, or None to remove it) as the process-wide LZ4
+    dictionary of the host entry points (tyche_lz4_use_dict): pages whose length plus the
+    dictionary's is at most 65,536 bytes are compressed against it and need it to be restored."""
+    _lib.check(_lib.load().tyche_lz4_use_dict(dictionary.handle if dictionary is not None else None),
+               "tyche_lz4_use_dict")
+
+
 def free_ptr(p: int | None) -> None:
     if p:
         _libc.free(p)

@@ -14,6 +14,12 @@ directions; rows above 65,535 bytes take the large-page kernels and still
 become one standard LZ4 block each.  zlib and zstd compress rows of up to
 65,535 bytes, and so does LZ4 under ``LZ4_EXACT=1``; beyond a limit the call
 raises ``DeviceError`` (``TYCHE_E_BAD_ARGS``, the limit in the message).
+
+Shared dictionary (LZ4 only): ``dictionary=Lz4Dict(bytes)`` makes the dictionary
+and each row one LZ4 window -- the blocks are what
+``LZ4_decompress_safe_usingDict`` restores, and need the same dictionary to be
+decoded.  Row length (capacity, when decoding) plus dictionary may not exceed
+65,536 bytes.
 """
 from __future__ import annotations
 
@@ -51,8 +57,57 @@ def _check_pages(t: torch.Tensor, name: str) -> None:
         raise ValueError(f"{name} must be a contiguous 2-D uint8 tensor")
 
 
+class Lz4Dict:
+    """A shared LZ4 dictionary (tyche_lz4_dict_create): 1..LZ4_DICT_MAX bytes, copied, immutable.
+    The engine uploads it to a device the first time a launch there uses it."""
+
+    def __init__(self, data: bytes):
+        data = bytes(data)
+        self._lib = _lib.load()
+        self.handle = self._lib.tyche_lz4_dict_create(data, len(data))
+        if not self.handle:
+            raise ValueError(_lib.last_error())
+        self.length = len(data)
+
+    def __len__(self) -> int:
+        return self.length
+
+    def close(self) -> None:
+        """Drops this reference; a process-wide installation or a launch in flight keeps its own."""
+        if self.handle:
+            self._lib.tyche_lz4_dict_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _compress_call(compressor_id: int, level: int, b, stream: int, dictionary) -> None:
+    if dictionary is None:
+        _lib.check(_lib.load().tyche_compress_batch(compressor_id, level, ctypes.byref(b), stream), "tyche_compress_batch")
+        return
+    if compressor_id != LZ4_COMPRESSOR_ID:
+        raise ValueError("dictionary= is an LZ4 feature")
+    _lib.check(_lib.load().tyche_lz4_compress_batch_dict(dictionary.handle, ctypes.byref(b), stream),
+               "tyche_lz4_compress_batch_dict")
+
+
+def _decompress_call(compressor_id: int, b, stream: int, dictionary) -> None:
+    if dictionary is None:
+        _lib.check(_lib.load().tyche_decompress_batch(compressor_id, ctypes.byref(b), stream), "tyche_decompress_batch")
+        return
+    if compressor_id != LZ4_COMPRESSOR_ID:
+        raise ValueError("dictionary= is an LZ4 feature")
+    _lib.check(_lib.load().tyche_lz4_decompress_batch_dict(dictionary.handle, ctypes.byref(b), stream),
+               "tyche_lz4_decompress_batch_dict")
+
+
 def compress_pages(pages: torch.Tensor, compressor_id: int = LZ4_COMPRESSOR_ID, level: int = 1,
-                   out: torch.Tensor | None = None, out_len: torch.Tensor | None = None):
+                   out: torch.Tensor | None = None, out_len: torch.Tensor | None = None,
+                   dictionary: Lz4Dict | None = None):
     """Compress every row of ``pages``; returns (slots, comp_len).
 
     comp_len[i] is LZ4_compress_default's return for row i (compressed bytes,
@@ -69,14 +124,13 @@ def compress_pages(pages: torch.Tensor, compressor_id: int = LZ4_COMPRESSOR_ID, 
     _check_pages(out, "out")
     b = _lib.Batch(count=n, src=_ptr(pages), src_stride=page_len, src_length=page_len, max_src_length=page_len,
                    dst=_ptr(out), dst_stride=out.shape[1], dst_capacity=out.shape[1], results=_ptr(out_len))
-    rc = _lib.load().tyche_compress_batch(compressor_id, level, ctypes.byref(b), _stream_handle(pages.device))
-    _lib.check(rc, "tyche_compress_batch")
+    _compress_call(compressor_id, level, b, _stream_handle(pages.device), dictionary)
     return out, out_len
 
 
 def decompress_pages(slots: torch.Tensor, comp_len: torch.Tensor, page_len: int,
                      compressor_id: int = LZ4_COMPRESSOR_ID, out: torch.Tensor | None = None,
-                     rv: torch.Tensor | None = None, max_comp_len: int = 0):
+                     rv: torch.Tensor | None = None, max_comp_len: int = 0, dictionary: Lz4Dict | None = None):
     """Decompress row i of ``slots`` (comp_len[i] bytes) into a page_len row.
 
     rv[i] is LZ4_decompress_safe's return (decoded size, or -(consumed)-1).
@@ -96,34 +150,31 @@ def decompress_pages(slots: torch.Tensor, comp_len: torch.Tensor, page_len: int,
     b = _lib.Batch(count=n, src=_ptr(slots), src_lengths=_ptr(comp_len), src_stride=slots.shape[1],
                    max_src_length=min(cap, slots.shape[1]), dst=_ptr(out), dst_stride=out.shape[1],
                    dst_capacity=page_len, results=_ptr(rv))
-    rc = _lib.load().tyche_decompress_batch(compressor_id, ctypes.byref(b), _stream_handle(slots.device))
-    _lib.check(rc, "tyche_decompress_batch")
+    _decompress_call(compressor_id, b, _stream_handle(slots.device), dictionary)
     return out, rv
 
 
 def decompress_ragged(stream: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, capacities: torch.Tensor,
                       out: torch.Tensor, out_offsets: torch.Tensor, rv: torch.Tensor, max_src_length: int,
-                      max_capacity: int, compressor_id: int = LZ4_COMPRESSOR_ID):
+                      max_capacity: int, compressor_id: int = LZ4_COMPRESSOR_ID, dictionary: Lz4Dict | None = None):
     """General form: page i = stream[offsets[i] : offsets[i]+lengths[i]] -> out[out_offsets[i] : +capacities[i]]."""
     b = _lib.Batch(count=offsets.numel(), src=_ptr(stream), src_offsets=_ptr(offsets), src_lengths=_ptr(lengths),
                    max_src_length=max_src_length, dst=_ptr(out), dst_offsets=_ptr(out_offsets),
                    dst_capacities=_ptr(capacities), dst_capacity=max_capacity, results=_ptr(rv))
-    rc = _lib.load().tyche_decompress_batch(compressor_id, ctypes.byref(b), _stream_handle(stream.device))
-    _lib.check(rc, "tyche_decompress_batch")
+    _decompress_call(compressor_id, b, _stream_handle(stream.device), dictionary)
     return out, rv
 
 
 def compress_ragged(src: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, out: torch.Tensor,
                     out_offsets: torch.Tensor, capacities: torch.Tensor, results: torch.Tensor, max_src_length: int,
-                    compressor_id: int = LZ4_COMPRESSOR_ID, level: int = 1):
+                    compressor_id: int = LZ4_COMPRESSOR_ID, level: int = 1, dictionary: Lz4Dict | None = None):
     """General form of compress_pages.  ``max_src_length`` declares the longest page (0: at most
     65,535 bytes); a longer page gets INT32_MIN.  With LZ4 it may be up to 4 MiB, and in a batch
     that mixes sizes the pages of up to 65,535 bytes get the bytes they would get on their own."""
     b = _lib.Batch(count=offsets.numel(), src=_ptr(src), src_offsets=_ptr(offsets), src_lengths=_ptr(lengths),
                    max_src_length=max_src_length, dst=_ptr(out), dst_offsets=_ptr(out_offsets),
                    dst_capacities=_ptr(capacities), results=_ptr(results))
-    rc = _lib.load().tyche_compress_batch(compressor_id, level, ctypes.byref(b), _stream_handle(src.device))
-    _lib.check(rc, "tyche_compress_batch")
+    _compress_call(compressor_id, level, b, _stream_handle(src.device), dictionary)
     return out, results
 
 

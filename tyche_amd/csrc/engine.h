@@ -85,6 +85,25 @@ hipError_t launch_lz4_encode_exact(const tyche_batch_t &b, uint32_t in_cap, hipS
 hipError_t launch_lz4_encode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t min_len, hipStream_t s);
 // launches beyond the LDS of the other decoders, up to TYCHE_LZ4_MAX_PAGE (lz4_decode_large.hip)
 hipError_t launch_lz4_decode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
+// A shared LZ4 dictionary's image on one device (engine.hip builds and uploads it once per handle
+// and device): `dec` is dpad bytes (a multiple of 16) with the dictionary's dlen bytes at their end;
+// `table` the 4,096 16-bit positions of the encoder's read-only dictionary table; `enc` 16 images
+// of enc_stride = enc_len + 16 bytes, image h holding the dictionary's last enc_len = dlen & ~63
+// bytes from byte h on (zeros around them).
+struct Lz4DictDev {
+    const uint8_t *dec;
+    const uint16_t *table;
+    const uint8_t *enc;
+    uint32_t dlen, dpad, enc_len, enc_stride;
+};
+// LZ4 with a shared dictionary (lz4_encode_dict.hip, lz4_decode_dict.hip): dictionary + page is one
+// window of at most 65,536 bytes.  per_page: pages beyond that reach are skipped, their results
+// left alone (the host entry points run the plain kernels over the same batch for them); else
+// in_cap / out_cap + dlen must not exceed it.
+hipError_t launch_lz4_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, bool per_page,
+                                  hipStream_t s);
+hipError_t launch_lz4_decode_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &d,
+                                  bool per_page, hipStream_t s);
 hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);

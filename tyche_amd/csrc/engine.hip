@@ -481,14 +481,18 @@ bool valid_codec(int id) {
     return id == TYCHE_LZ4_COMPRESSOR_ID || id == TYCHE_ZLIB_COMPRESSOR_ID || id == TYCHE_ZSTD_COMPRESSOR_ID;
 }
 
-// the encoder kernel for a codec id (valid_codec)
-hipError_t launch_encode(int id, const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
-    // Test hook (TYCHE_FAIL_COMPRESS_EVERY=N or the knob): every Nth encode launch
-    // fails as a lost device would, so the callers' TYCHE_E_DEVICE handling
-    // (list.c:1051-1060 and the INTEGRATION.md change) can be exercised.
+// Test hook (TYCHE_FAIL_COMPRESS_EVERY=N or the knob): every Nth encode launch
+// fails as a lost device would, so the callers' TYCHE_E_DEVICE handling
+// (list.c:1051-1060 and the INTEGRATION.md change) can be exercised.
+bool compress_launch_fails() {
     static std::atomic<unsigned long> launches{0};
     const long every = knob("FAIL_COMPRESS_EVERY", 0);
-    if (every > 0 && (launches.fetch_add(1) + 1) % (unsigned long)every == 0) return hipErrorLaunchFailure;
+    return every > 0 && (launches.fetch_add(1) + 1) % (unsigned long)every == 0;
+}
+
+// the encoder kernel for a codec id (valid_codec)
+hipError_t launch_encode(int id, const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
+    if (compress_launch_fails()) return hipErrorLaunchFailure;
     if (id == TYCHE_ZSTD_COMPRESSOR_ID) return launch_zstd_encode(b, in_cap, s);
     if (id == TYCHE_ZLIB_COMPRESSOR_ID) return launch_zlib_deflate(b, in_cap, s);
     return launch_lz4_encode(b, in_cap, s);
@@ -1293,6 +1297,182 @@ int run_host(size_t n, const void *const *src, const uint32_t *src_len, void *co
     return TYCHE_E_OK;
 }
 
+// ------------------------------------------------------ shared LZ4 dictionary
+// A handle is immutable after creation: the bytes, the encoder's dictionary table and the device
+// image (engine.h: Lz4DictDev) are built once on the host; the image is uploaded to a device the
+// first time a launch there needs it, under the handle's lock.  References: the creator's (dropped
+// by tyche_lz4_dict_destroy), the process-wide slot's, and one per host call that runs with the
+// process-wide dictionary.  The last one frees the device copies with hipFree, which returns only
+// once the device has finished the work submitted before it -- a launch still in flight on a
+// caller's stream keeps reading valid memory until it ends.
+}  // namespace
+
+struct tyche_lz4_dict {
+    std::atomic<long> refs{1};
+    uint32_t len = 0, dpad = 0, enc_len = 0, enc_stride = 0;
+    std::vector<uint8_t> image;   // dec (dpad) | table (8 KiB) | enc (16 x enc_stride)
+    std::mutex mu;
+    uint8_t *dev[kMaxDevices] = {};
+};
+namespace {
+constexpr size_t kDictTableBytes = 4096 * sizeof(uint16_t);
+// the encoder's table key (lz_parse.h's hash5 at TYCHE_HASH_LOG 12, lz4_encode_dict.hip): 5 bytes
+inline uint32_t dict_hash(const uint8_t *p) {
+    uint64_t x = 0;
+    memcpy(&x, p, 5);
+    return (uint32_t)((x * 0xCF1BBCDCB7A56463ull) >> 52);
+}
+
+void dict_retain(const tyche_lz4_dict *d) { const_cast<tyche_lz4_dict *>(d)->refs.fetch_add(1); }
+void dict_release(const tyche_lz4_dict *cd) {
+    tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
+    if (!d || d->refs.fetch_sub(1) != 1) return;
+    DeviceGuard keep;
+    for (int i = 0; i < kMaxDevices; i++)
+        if (d->dev[i] && hipSetDevice(i) == hipSuccess) (void)hipFree(d->dev[i]);
+    delete d;
+}
+
+// the handle's image on the current device, uploaded on first use
+int dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, hipError_t *why = nullptr) {
+    tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return (why ? (void)(*why = e) : (void)0), fail("hipGetDevice", e);
+    if (dev < 0 || dev >= kMaxDevices) return (why ? (void)(*why = hipErrorInvalidDevice) : (void)0), fail_msg("selected device out of range");
+    std::lock_guard<std::mutex> g(d->mu);
+    if (!d->dev[dev]) {
+        uint8_t *p = nullptr;
+        if ((e = hipMalloc((void **)&p, d->image.size())) != hipSuccess) {
+            if (why) *why = e;
+            return fail("hipMalloc(dictionary)", e);
+        }
+        if ((e = hipMemcpy(p, d->image.data(), d->image.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+            (void)hipFree(p);
+            if (why) *why = e;
+            return fail("hipMemcpy(dictionary)", e);
+        }
+        d->dev[dev] = p;
+    }
+    out->dec = d->dev[dev];
+    out->table = (const uint16_t *)(d->dev[dev] + d->dpad);
+    out->enc = d->dev[dev] + d->dpad + kDictTableBytes;
+    out->dlen = d->len;
+    out->dpad = d->dpad;
+    out->enc_len = d->enc_len;
+    out->enc_stride = d->enc_stride;
+    return TYCHE_E_OK;
+}
+
+tyche_lz4_dict *dict_create(const void *bytes, uint32_t len) {
+    if (!bytes || len == 0 || len > TYCHE_LZ4_DICT_MAX) {
+        t_error = "an LZ4 dictionary holds 1 to TYCHE_LZ4_DICT_MAX (" + std::to_string(TYCHE_LZ4_DICT_MAX) +
+                  ") bytes; got " + (bytes ? std::to_string(len) : std::string("NULL"));
+        return nullptr;
+    }
+    tyche_lz4_dict *d = new tyche_lz4_dict();
+    const uint8_t *src = (const uint8_t *)bytes;
+    d->len = len;
+    d->dpad = (len + 15u) & ~15u;
+    d->enc_len = len & ~63u;
+    d->enc_stride = d->enc_len + 16u;
+    d->image.assign((size_t)d->dpad + kDictTableBytes + 16u * (size_t)d->enc_stride, 0);
+    memcpy(d->image.data() + (d->dpad - len), src, len);
+    // every position of the encoder's part whose 5 hashed bytes lie inside it, the last of equal hashes kept
+    // (window position j = byte j of the part); an empty slot is position 0, as in a zeroed table
+    const uint8_t *tail = src + (len - d->enc_len);
+    uint16_t *table = (uint16_t *)(d->image.data() + d->dpad);
+    for (uint32_t j = 0; j + 5u <= d->enc_len; j++) table[dict_hash(tail + j)] = (uint16_t)j;
+    uint8_t *enc = d->image.data() + d->dpad + kDictTableBytes;
+    for (uint32_t h = 0; h < 16u; h++) memcpy(enc + (size_t)h * d->enc_stride + h, tail, d->enc_len);
+    return d;
+}
+
+// The process-wide dictionary of the host entry points.  Heap state that is never destroyed: a
+// restore dispatcher may still run a batch at exit().
+struct DictSlot {
+    std::mutex mu;
+    const tyche_lz4_dict *d = nullptr;
+    bool env_done = false;
+    std::string env_error;   // TYCHE_LZ4_DICT named a file that cannot serve: every LZ4 host call fails with it
+};
+DictSlot &dict_slot() {
+    static DictSlot &s = *new DictSlot();
+    return s;
+}
+// TYCHE_LZ4_DICT=<file>, read once (slot locked)
+void dict_env_locked(DictSlot &S) {
+    if (S.env_done) return;
+    S.env_done = true;
+    const char *path = getenv("TYCHE_LZ4_DICT");
+    if (!path || !*path) return;
+    std::vector<uint8_t> buf(TYCHE_LZ4_DICT_MAX + 1u);
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        S.env_error = std::string("TYCHE_LZ4_DICT: cannot read ") + path;
+        return;
+    }
+    const size_t n = fread(buf.data(), 1, buf.size(), f);
+    fclose(f);
+    if (n == 0 || n > TYCHE_LZ4_DICT_MAX) {
+        S.env_error = std::string("TYCHE_LZ4_DICT: ") + path + (n == 0 ? " is empty" : " is longer than TYCHE_LZ4_DICT_MAX (" +
+                      std::to_string(TYCHE_LZ4_DICT_MAX) + " bytes)");
+        return;
+    }
+    S.d = dict_create(buf.data(), (uint32_t)n);
+}
+// The dictionary an LZ4 host call runs with (retained: the caller releases it), or NULL.
+// TYCHE_E_BAD_ARGS when the environment names a dictionary file that cannot serve.
+int dict_for_host_call(const tyche_lz4_dict **out) {
+    DictSlot &S = dict_slot();
+    std::lock_guard<std::mutex> g(S.mu);
+    dict_env_locked(S);
+    *out = nullptr;
+    if (!S.env_error.empty()) {
+        t_error = S.env_error;
+        return TYCHE_E_BAD_ARGS;
+    }
+    if (S.d) {
+        dict_retain(S.d);
+        *out = S.d;
+    }
+    return TYCHE_E_OK;
+}
+struct DictHold {
+    const tyche_lz4_dict *d = nullptr;
+    ~DictHold() { dict_release(d); }
+};
+// Why a dictionary upload inside a host-path launch failed.  The launch may run on a fan-out worker
+// thread, whose t_error the caller never sees, and run_host names only "kernel launch": the first
+// reason is kept here and put back into the calling thread's t_error after the batch.
+struct DictUploadNote {
+    std::mutex mu;
+    std::string msg;
+    hipError_t upload(const tyche_lz4_dict *d, Lz4DictDev *img) {
+        hipError_t why = hipErrorUnknown;
+        if (dict_on_device(d, img, &why) == TYCHE_E_OK) return hipSuccess;
+        std::lock_guard<std::mutex> g(mu);
+        if (msg.empty()) msg = t_error;
+        return why;
+    }
+    int finish(int rc) {
+        if (rc != TYCHE_E_OK && !msg.empty()) {
+            t_error = msg;
+            log_error(t_error);
+        }
+        return rc;
+    }
+};
+int dict_exact_conflict() {
+    t_error = "LZ4_EXACT=1 and an LZ4 dictionary do not combine: exact mode promises LZ4_compress_default's bytes";
+    return TYCHE_E_BAD_ARGS;
+}
+int dict_reach_error(const char *what, uint32_t cap, uint32_t dlen) {
+    t_error = std::string("LZ4 dictionary reach: ") + what + " (" + std::to_string(cap) + ") plus the dictionary (" +
+              std::to_string(dlen) + " bytes) exceeds 65536";
+    return TYCHE_E_BAD_ARGS;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1437,6 +1617,64 @@ int tyche_decompress_batch(int compressor_id, const tyche_batch_t *batch, void *
     return TYCHE_E_OK;
 }
 
+// ------------------------------------------------- shared LZ4 dictionary API
+tyche_lz4_dict_t *tyche_lz4_dict_create(const void *bytes, uint32_t len) { return dict_create(bytes, len); }
+
+void tyche_lz4_dict_destroy(tyche_lz4_dict_t *d) { dict_release(d); }
+
+uint32_t tyche_lz4_dict_length(const tyche_lz4_dict_t *d) { return d ? d->len : 0u; }
+
+int tyche_lz4_use_dict(const tyche_lz4_dict_t *d) {
+    DictSlot &S = dict_slot();
+    const tyche_lz4_dict *old;
+    {
+        std::lock_guard<std::mutex> g(S.mu);
+        S.env_done = true;   // an explicit choice replaces whatever TYCHE_LZ4_DICT names
+        S.env_error.clear();
+        old = S.d;
+        if (d) dict_retain(d);
+        S.d = d;
+    }
+    dict_release(old);
+    return TYCHE_E_OK;
+}
+
+int tyche_lz4_compress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream) {
+    if (!d || !batch) return TYCHE_E_BAD_ARGS;
+    if (knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
+    if (batch->count == 0) return TYCHE_E_OK;
+    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
+    uint32_t in_cap = batch->src_lengths ? batch->max_src_length : batch->src_length;
+    if (batch->src_lengths && in_cap == 0) in_cap = 65535;
+    if ((uint64_t)in_cap + d->len > 65536u) return dict_reach_error("the launch's largest page", in_cap, d->len);
+    DeviceGuard keep;
+    if (int rc = stream_device((hipStream_t)stream)) return rc;
+    Lz4DictDev img;
+    if (int rc = dict_on_device(d, &img)) return rc;
+    hipError_t e = compress_launch_fails() ? hipErrorLaunchFailure   // the FAIL_COMPRESS_EVERY test hook, as launch_encode
+                                           : launch_lz4_encode_dict(*batch, in_cap, img, false, (hipStream_t)stream);
+    if (e != hipSuccess) return fail("lz4 dictionary encode launch", e);
+    return TYCHE_E_OK;
+}
+
+int tyche_lz4_decompress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream) {
+    if (!d || !batch) return TYCHE_E_BAD_ARGS;
+    if (batch->count == 0) return TYCHE_E_OK;
+    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
+    const uint32_t out_cap = batch->dst_capacity;
+    if ((uint64_t)out_cap + d->len > 65536u) return dict_reach_error("the launch's largest capacity", out_cap, d->len);
+    DeviceGuard keep;
+    if (int rc = stream_device((hipStream_t)stream)) return rc;
+    Lz4DictDev img;
+    if (int rc = dict_on_device(d, &img)) return rc;
+    // (a declared stream maximum is only a bound: above the longest stream a 65,536-byte window can
+    // need it is taken as that, and a page whose stream is longer still gets INT32_MIN)
+    const uint32_t in_cap = std::min(decode_in_cap(*batch, lz4_bound(out_cap)), lz4_bound(65536u));
+    hipError_t e = launch_lz4_decode_dict(*batch, in_cap, out_cap, img, false, (hipStream_t)stream);
+    if (e != hipSuccess) return fail("lz4 dictionary decode launch", e);
+    return TYCHE_E_OK;
+}
+
 // ----------------------------------------------------------- host batch API
 int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const void *const *src,
                         const uint32_t *src_lengths, void *const *dst, const uint32_t *dst_capacities,
@@ -1450,6 +1688,29 @@ int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const
     // LZ4's encoders only store to their destination (never read it back), so their streams may go
     // straight into the pinned staging arena (HOST_DIRECT_OUT=0: stage through HBM and D2H instead)
     const int direct = compressor_id == TYCHE_LZ4_COMPRESSOR_ID && knob("HOST_DIRECT_OUT", 1) ? kDirectAlways : kDirectNone;
+    // LZ4 with a process-wide dictionary: the pages it reaches (length + dictionary <= 65536) take
+    // the dictionary encoder; a chunk that also holds longer pages runs today's launch first, for
+    // their bytes, and the dictionary launch then writes the pages in reach over it.
+    DictHold dict;
+    if (compressor_id == TYCHE_LZ4_COMPRESSOR_ID) {
+        if (int rc = dict_for_host_call(&dict.d)) return rc;
+        if (dict.d && knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
+    }
+    if (const tyche_lz4_dict *d = dict.d) {
+        DictUploadNote note;
+        return note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
+                        [d, &note](const tyche_batch_t &b, hipStream_t s, bool) {
+                            Lz4DictDev img;
+                            if (const hipError_t ue = note.upload(d, &img)) return ue;
+                            const uint32_t longest = std::max(b.max_src_length, 1u), reach = 65536u - d->len;
+                            if (longest <= reach)
+                                return compress_launch_fails() ? hipErrorLaunchFailure
+                                                               : launch_lz4_encode_dict(b, longest, img, false, s);
+                            const hipError_t e = launch_encode(TYCHE_LZ4_COMPRESSOR_ID, b, longest, s);
+                            if (e != hipSuccess) return e;
+                            return launch_lz4_encode_dict(b, reach, img, true, s);
+                        }, false, direct));
+    }
     return run_host(n, src, src_lengths, dst, dst_capacities, results,
                           [compressor_id](const tyche_batch_t &b, hipStream_t s, bool) {
                               return launch_encode(compressor_id, b, std::max(b.max_src_length, 1u), s);
@@ -1482,11 +1743,26 @@ int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, c
     size_t n_small = 0, n_large = 0;
     for (size_t i = 0; i < n; i++) (dst_capacities[i] <= 65536u ? n_small : n_large)++;
     const bool mixed_bulk = n_large > 0 && n_small > kBulkSmallMax;
-    const int rc = run_host(n, src, src_lengths, dst, dst_capacities, results,
-                          [mixed_bulk](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
+    // With a process-wide dictionary the pages it reaches (capacity + dictionary <= 65536) take the
+    // dictionary decoder; a chunk that also holds larger capacities runs today's launch first, for
+    // them, and the dictionary launch then decodes the pages in reach over whatever that left.
+    DictHold dict;
+    if (int rc = dict_for_host_call(&dict.d)) return rc;
+    const tyche_lz4_dict *d = dict.d;
+    DictUploadNote note;
+    const int rc = note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
+                          [mixed_bulk, d, &note](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
                               if (mixed_bulk && b.dst_capacity > 65536u) return hipErrorInvalidValue;
-                              return launch_lz4_decode(b, b.max_src_length, b.dst_capacity, s, !host_dst);
-                          }, true, knob("HOST_DIRECT_OUT", 1) ? kDirectLz4Decode : kDirectNone);
+                              if (!d) return launch_lz4_decode(b, b.max_src_length, b.dst_capacity, s, !host_dst);
+                              Lz4DictDev img;
+                              if (const hipError_t ue = note.upload(d, &img)) return ue;
+                              const uint32_t reach = 65536u - d->len;
+                              const uint32_t in_cap = std::min(b.max_src_length, lz4_bound(65536u));
+                              if (b.dst_capacity <= reach) return launch_lz4_decode_dict(b, in_cap, b.dst_capacity, img, false, s);
+                              const hipError_t e = launch_lz4_decode(b, b.max_src_length, b.dst_capacity, s, !host_dst);
+                              if (e != hipSuccess) return e;
+                              return launch_lz4_decode_dict(b, in_cap, reach, img, true, s);
+                          }, true, knob("HOST_DIRECT_OUT", 1) ? kDirectLz4Decode : kDirectNone));
     if (rc == TYCHE_E_DEVICE && mixed_bulk)
         t_error += " (an LZ4 host batch with a capacity above 65536 bytes beside more than " + std::to_string(kBulkSmallMax) +
                    " pages of at most that is refused: pass the large pages in a call of their own)";

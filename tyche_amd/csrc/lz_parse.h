@@ -68,6 +68,16 @@ __device__ __forceinline__ uint32_t phase_clock() { return (uint32_t)__builtin_a
 #endif
 
 __device__ __forceinline__ uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - kHashLog); }
+// TYCHE_PARSE_HASH5 (set by the including translation unit; lz4_encode_dict.hip): the single-slot
+// table is keyed by 5 bytes, v and the low byte of the word after it, as the reference's stream
+// mode is on 64-bit hosts (LZ4_hash5, lz4.c:410, 423) -- a table seeded with a whole dictionary then
+// keeps candidates that agree in one byte more, instead of the latest of every 4-byte value
+#ifndef TYCHE_PARSE_HASH5
+#define TYCHE_PARSE_HASH5 0
+#endif
+__device__ __forceinline__ uint32_t hash5(uint32_t v, uint32_t next) {
+    return (uint32_t)(((((uint64_t)(next & 0xFFu) << 32) | v) * 0xCF1BBCDCB7A56463ull) >> (64 - kHashLog));
+}
 
 // The page is read as aligned dwords only: an LDS read off its natural
 // alignment (a 4-byte read at an odd address, a b64/b128 off 8/16) is replayed
@@ -348,7 +358,7 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
             const uint32_t h = kRepCand && TYCHE_HASH_BYTES > 4
                                    ? (uint32_t)(((((uint64_t)(pw.fw[0] & (TYCHE_HASH_BYTES == 5 ? 0xFFu : 0xFFFFu)) << 32) | v) *
                                                  0xCF1BBCDCB7A56463ull) >> (64 - kHashLog))
-                                   : hash4(v);
+                                   : TYCHE_PARSE_HASH5 ? hash5(v, pw.fw[0]) : hash4(v);
             if (kLaneAddr && !kRepCand) {
                 lds_u16_t *slot = (lds_u16_t *)(uintptr_t)slot_addr(tbase, h);
                 cands[0] = *slot;
