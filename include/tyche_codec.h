@@ -245,6 +245,49 @@ int tyche_lz4_decompress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch
 /* process-wide dictionary of the host entry points (Buffer API, tyche_buffers_*, host batches,
  * restore queue, multi-device fan-out); NULL removes it.  Holds a reference of its own. */
 int tyche_lz4_use_dict(const tyche_lz4_dict_t *d);
+/* copies min(cap, length) dictionary bytes out; returns the length */
+uint32_t tyche_lz4_dict_bytes(const tyche_lz4_dict_t *d, void *out, uint32_t cap);
+/* a new reference to the process-wide dictionary (tyche_lz4_dict_destroy drops it), or NULL */
+tyche_lz4_dict_t *tyche_lz4_current_dict(void);
+
+/* ---- training a dictionary from sample pages ------------------------------ */
+/* The trainer picks the 128-byte segments of the sample pages whose 8-byte keys occur in the most
+ * other pages, one segment per round, each round discounting what earlier picks already cover
+ * (DESIGN.md 3.3d has the algorithm, which defines the bytes: they depend on the pages, their order
+ * and dict_len alone, not on the device, the batch layout or the run).  The dictionary is
+ * 128 x picks <= dict_len bytes long, the most valuable segment last, where every page can reach it.
+ * It runs on the GPU; nothing falls back to the CPU.
+ *
+ * tyche_lz4_dict_train_batch trains on a device-resident batch (src, src_offsets | src_stride,
+ * src_lengths | src_length, count and, beside src_lengths, max_src_length, 0 there meaning 65535;
+ * the dst fields and results are ignored) on `stream`, waits for it, and returns a new handle --
+ * an ordinary immutable dictionary handle, as from tyche_lz4_dict_create.  tyche_lz4_dict_train_host
+ * does the same from host pages.  NULL with the rule and the numbers in tyche_last_error() when:
+ * dict_len is outside 128..TYCHE_LZ4_DICT_MAX; count is 0 or above TYCHE_LZ4_TRAIN_MAX_PAGES; a page
+ * (or the declared maximum) is above 65535 bytes; the pages hold more than TYCHE_LZ4_TRAIN_MAX_BYTES
+ * in total; there is no usable device; or nothing was picked ("the sample pages share no content":
+ * no 8-byte key occurs in two pages).
+ *
+ * TYCHE_LZ4_DICT_AUTO=<bytes> in the environment (opt-in; 128..TYCHE_LZ4_DICT_MAX): the host LZ4
+ * compress entry points (buffer__compress, tyche_buffers_compress, tyche_compress_host) copy the
+ * pages they are given -- those of at least 128 bytes that the dictionary will reach, length +
+ * <bytes> <= 65536 -- into a sample buffer until TYCHE_LZ4_DICT_AUTO_PAGES pages (default 256) or
+ * TYCHE_LZ4_TRAIN_MAX_BYTES are collected, compressing exactly as without a dictionary meanwhile.
+ * The call that completes the sample trains after its own pages are compressed and installs the
+ * result process-wide, once; concurrent callers never wait for the training and compress plain
+ * until the install is visible.  A plain block is also a valid dictionary block (its offsets never
+ * reach the dictionary), so pages compressed before the install restore through the dictionary
+ * decoder afterwards.  If training yields nothing, auto mode ends, the process stays plain and
+ * the reason is in tyche_last_error() on the training thread.  The trainer never replaces an
+ * installed dictionary: a tyche_lz4_use_dict call made while samples are collected (or while the
+ * training runs) ends auto mode and wins.  TYCHE_LZ4_DICT and TYCHE_LZ4_DICT_AUTO both set, or a
+ * malformed value, make every LZ4 host call fail with TYCHE_E_BAD_ARGS and the reason; LZ4_EXACT=1
+ * with auto mode is the does-not-combine error above. */
+#define TYCHE_LZ4_TRAIN_MAX_BYTES (64u << 20)
+#define TYCHE_LZ4_TRAIN_MAX_PAGES (1u << 19)
+tyche_lz4_dict_t *tyche_lz4_dict_train_batch(const tyche_batch_t *samples, uint32_t dict_len, void *stream);
+tyche_lz4_dict_t *tyche_lz4_dict_train_host(size_t n, const void *const *src, const uint32_t *src_lengths,
+                                            uint32_t dict_len);
 
 /* ---- host batch API (pinned staging + H2D -> kernels -> D2H) ------------- */
 /* Same per-page semantics as the device batch, with host pointers.  Used by

@@ -35,6 +35,8 @@ ALL_DEVICES = -1        # tyche_set_device: spread host work over the device set
 
 RESULT_TOO_LARGE = -(2 ** 31)
 LZ4_DICT_MAX = 32768    # TYCHE_LZ4_DICT_MAX
+LZ4_TRAIN_MAX_BYTES = 64 << 20   # TYCHE_LZ4_TRAIN_MAX_BYTES
+LZ4_TRAIN_MAX_PAGES = 1 << 19    # TYCHE_LZ4_TRAIN_MAX_PAGES
 
 # buffer flags, src/buffer.h:23-33
 FLAG_COMPRESSING = 1 << 5
@@ -114,6 +116,10 @@ SIGNATURES = {
     "tyche_lz4_compress_batch_dict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Batch), ctypes.c_void_p]),
     "tyche_lz4_decompress_batch_dict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Batch), ctypes.c_void_p]),
     "tyche_lz4_use_dict": (ctypes.c_int, [ctypes.c_void_p]),
+    "tyche_lz4_dict_bytes": (ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "tyche_lz4_current_dict": (ctypes.c_void_p, []),
+    "tyche_lz4_dict_train_batch": (ctypes.c_void_p, [ctypes.POINTER(Batch), ctypes.c_uint32, ctypes.c_void_p]),
+    "tyche_lz4_dict_train_host": (ctypes.c_void_p, [ctypes.c_size_t, _vpp, _u32p, ctypes.c_uint32]),
     "tyche_compress_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, _vpp, _u32p, _vpp, _u32p,
                                            _i32p]),
     "tyche_decompress_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, _vpp, _u32p, _vpp, _u32p, _i32p]),

@@ -19,7 +19,8 @@ Shared dictionary (LZ4 only): ``dictionary=Lz4Dict(bytes)`` makes the dictionary
 and each row one LZ4 window -- the blocks are what
 ``LZ4_decompress_safe_usingDict`` restores, and need the same dictionary to be
 decoded.  Row length (capacity, when decoding) plus dictionary may not exceed
-65,536 bytes.
+65,536 bytes.  ``Lz4Dict.train(pages, length)`` makes one from sample pages on
+the GPU; ``Lz4Dict.data`` returns a dictionary's bytes.
 """
 from __future__ import annotations
 
@@ -68,6 +69,45 @@ class Lz4Dict:
         if not self.handle:
             raise ValueError(_lib.last_error())
         self.length = len(data)
+
+    @classmethod
+    def _from_handle(cls, handle) -> "Lz4Dict":
+        d = cls.__new__(cls)
+        d._lib = _lib.load()
+        d.handle = handle
+        d.length = int(d._lib.tyche_lz4_dict_length(handle))
+        return d
+
+    @classmethod
+    def train(cls, pages, length: int) -> "Lz4Dict":
+        """Trains a dictionary of at most ``length`` bytes (128..LZ4_DICT_MAX) on the GPU
+        (tyche_lz4_dict_train_batch / _host): ``pages`` is an (n, page_len) uint8 device tensor, page_len
+        up to 65,535, or a list of ``bytes``.  Blocks until the dictionary is made; raises ValueError with
+        the engine's reason when it refuses (too few or too many samples, no device, pages that share
+        nothing)."""
+        lib = _lib.load()
+        if isinstance(pages, torch.Tensor):
+            _check_pages(pages, "pages")
+            n, page_len = pages.shape
+            b = _lib.Batch(count=n, src=_ptr(pages), src_stride=page_len, src_length=page_len, max_src_length=page_len)
+            handle = lib.tyche_lz4_dict_train_batch(ctypes.byref(b), int(length), _stream_handle(pages.device))
+        else:
+            pages = [bytes(p) for p in pages]
+            n = len(pages)
+            keep = [ctypes.create_string_buffer(p, max(len(p), 1)) for p in pages]
+            srcs = (ctypes.c_void_p * max(n, 1))(*[ctypes.addressof(k) for k in keep])
+            lens = (ctypes.c_uint32 * max(n, 1))(*[len(p) for p in pages])
+            handle = lib.tyche_lz4_dict_train_host(n, srcs, lens, int(length))
+        if not handle:
+            raise ValueError(_lib.last_error())
+        return cls._from_handle(handle)
+
+    @property
+    def data(self) -> bytes:
+        """The dictionary's bytes."""
+        out = ctypes.create_string_buffer(max(self.length, 1))
+        n = self._lib.tyche_lz4_dict_bytes(self.handle, out, self.length)
+        return out.raw[:n]
 
     def __len__(self) -> int:
         return self.length

@@ -104,6 +104,18 @@ hipError_t launch_lz4_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const
                                   hipStream_t s);
 hipError_t launch_lz4_decode_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &d,
                                   bool per_page, hipStream_t s);
+// Trains a shared LZ4 dictionary of up to dict_len bytes (128 .. TYCHE_LZ4_DICT_MAX) from the batch's source
+// pages on stream s and waits for it (lz4_dict_train.hip; the dst fields are ignored).  dict_out: dict_len
+// host bytes.  hipSuccess with res->too_long (a page above in_cap <= 65535) or res->total_bytes above
+// TYCHE_LZ4_TRAIN_MAX_BYTES means the training stopped after its count pass: the caller names the rule.
+struct TrainResult {
+    uint32_t dict_len = 0;   // bytes written to dict_out: 128 x picks, 0 when the pages share nothing
+    bool too_long = false;
+    uint64_t total_bytes = 0;
+    const char *step = "";   // what was being done when an error is returned
+};
+hipError_t train_lz4_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t dict_len, hipStream_t s, uint8_t *dict_out,
+                          TrainResult *res);
 hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);

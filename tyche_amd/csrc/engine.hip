@@ -1395,6 +1395,19 @@ struct DictSlot {
     const tyche_lz4_dict *d = nullptr;
     bool env_done = false;
     std::string env_error;   // TYCHE_LZ4_DICT named a file that cannot serve: every LZ4 host call fails with it
+    // TYCHE_LZ4_DICT_AUTO: the host compress calls collect sample pages (packed in `sample`, their
+    // lengths in `sample_len`) until auto_pages pages or TYCHE_LZ4_TRAIN_MAX_BYTES; the call that
+    // completes the sample takes it away (kAutoTraining) and trains outside the lock
+    enum { kAutoOff, kAutoCollecting, kAutoTraining } auto_state = kAutoOff;
+    uint32_t auto_len = 0;
+    size_t auto_pages = 256;
+    std::vector<uint8_t> sample;
+    std::vector<uint32_t> sample_len;
+    void end_auto() {
+        auto_state = kAutoOff;
+        std::vector<uint8_t>().swap(sample);
+        std::vector<uint32_t>().swap(sample_len);
+    }
 };
 DictSlot &dict_slot() {
     static DictSlot &s = *new DictSlot();
@@ -1405,6 +1418,31 @@ void dict_env_locked(DictSlot &S) {
     if (S.env_done) return;
     S.env_done = true;
     const char *path = getenv("TYCHE_LZ4_DICT");
+    if (const char *a = getenv("TYCHE_LZ4_DICT_AUTO"); a && *a) {
+        if (path && *path) {
+            S.env_error = "TYCHE_LZ4_DICT and TYCHE_LZ4_DICT_AUTO are both set: name a dictionary file or have one trained, not both";
+            return;
+        }
+        char *end = nullptr;
+        const long v = strtol(a, &end, 10);
+        if (end == a || *end || v < 128 || v > (long)TYCHE_LZ4_DICT_MAX) {
+            S.env_error = std::string("TYCHE_LZ4_DICT_AUTO: \"") + a + "\" is not a dictionary length of 128 to TYCHE_LZ4_DICT_MAX (" +
+                          std::to_string(TYCHE_LZ4_DICT_MAX) + ") bytes";
+            return;
+        }
+        if (const char *np = getenv("TYCHE_LZ4_DICT_AUTO_PAGES"); np && *np) {
+            const long k = strtol(np, &end, 10);
+            if (end == np || *end || k < 1 || k > (long)TYCHE_LZ4_TRAIN_MAX_PAGES) {
+                S.env_error = std::string("TYCHE_LZ4_DICT_AUTO_PAGES: \"") + np + "\" is not a page count of 1 to TYCHE_LZ4_TRAIN_MAX_PAGES (" +
+                              std::to_string(TYCHE_LZ4_TRAIN_MAX_PAGES) + ")";
+                return;
+            }
+            S.auto_pages = (size_t)k;
+        }
+        S.auto_len = (uint32_t)v;
+        S.auto_state = DictSlot::kAutoCollecting;
+        return;
+    }
     if (!path || !*path) return;
     std::vector<uint8_t> buf(TYCHE_LZ4_DICT_MAX + 1u);
     FILE *f = fopen(path, "rb");
@@ -1442,6 +1480,60 @@ struct DictHold {
     const tyche_lz4_dict *d = nullptr;
     ~DictHold() { dict_release(d); }
 };
+// TYCHE_LZ4_DICT_AUTO.  auto_collect copies a host compress call's eligible pages into the sample
+// (slot locked: a memcpy, never the training); the call that completes the sample gets it in *out
+// (dict_len != 0) and trains after compressing its own pages.
+struct AutoSample {
+    uint32_t dict_len = 0;
+    std::vector<uint8_t> data;
+    std::vector<uint32_t> len;
+};
+int dict_exact_conflict();
+int auto_collect(size_t n, const void *const *src, const uint32_t *src_lengths, AutoSample *out) {
+    DictSlot &S = dict_slot();
+    std::lock_guard<std::mutex> g(S.mu);
+    if (S.auto_state == DictSlot::kAutoOff) return TYCHE_E_OK;
+    if (knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
+    if (S.auto_state != DictSlot::kAutoCollecting) return TYCHE_E_OK;
+    bool full = false;
+    for (size_t i = 0; i < n && !full; i++) {
+        const uint32_t L = src_lengths[i];
+        if (L < 128u || (uint64_t)L + S.auto_len > 65536u) continue;
+        if (S.sample.size() + L > TYCHE_LZ4_TRAIN_MAX_BYTES) {
+            full = true;
+            break;
+        }
+        const uint8_t *p = (const uint8_t *)src[i];
+        S.sample.insert(S.sample.end(), p, p + L);
+        S.sample_len.push_back(L);
+        full = S.sample_len.size() >= S.auto_pages;
+    }
+    if (!full) return TYCHE_E_OK;
+    out->dict_len = S.auto_len;
+    out->data.swap(S.sample);
+    out->len.swap(S.sample_len);
+    S.auto_state = DictSlot::kAutoTraining;
+    return TYCHE_E_OK;
+}
+tyche_lz4_dict *train_packed(const uint8_t *data, const uint32_t *lens, size_t n, uint32_t dict_len);
+// Trains on the completed sample and installs the result, unless something was installed (or auto
+// mode ended: tyche_lz4_use_dict) meanwhile.  A failure leaves its reason in t_error and the
+// process plain.
+void auto_train_and_install(const AutoSample &a) {
+    tyche_lz4_dict *d = train_packed(a.data.data(), a.len.data(), a.len.size(), a.dict_len);
+    DictSlot &S = dict_slot();
+    {
+        std::lock_guard<std::mutex> g(S.mu);
+        if (S.auto_state == DictSlot::kAutoTraining) {
+            S.auto_state = DictSlot::kAutoOff;
+            if (d && !S.d) {
+                S.d = d;   // the slot takes the creator's reference
+                d = nullptr;
+            }
+        }
+    }
+    dict_release(d);
+}
 // Why a dictionary upload inside a host-path launch failed.  The launch may run on a fan-out worker
 // thread, whose t_error the caller never sees, and run_host names only "kernel launch": the first
 // reason is kept here and put back into the calling thread's t_error after the batch.
@@ -1471,6 +1563,81 @@ int dict_reach_error(const char *what, uint32_t cap, uint32_t dlen) {
     t_error = std::string("LZ4 dictionary reach: ") + what + " (" + std::to_string(cap) + ") plus the dictionary (" +
               std::to_string(dlen) + " bytes) exceeds 65536";
     return TYCHE_E_BAD_ARGS;
+}
+
+// ---- training (lz4_dict_train.hip).  The rules that need no device come first, so that they read
+// the same with and without one; each names itself and its numbers in t_error.
+std::nullptr_t train_refuse(const std::string &m) {
+    t_error = m;
+    log_error(t_error);
+    return nullptr;
+}
+bool train_args_ok(uint32_t dict_len, size_t count) {
+    if (dict_len < 128u || dict_len > TYCHE_LZ4_DICT_MAX)
+        return train_refuse("LZ4 dictionary training: dict_len (" + std::to_string(dict_len) + ") must be 128 to TYCHE_LZ4_DICT_MAX (" +
+                            std::to_string(TYCHE_LZ4_DICT_MAX) + ") bytes"), false;
+    if (count == 0) return train_refuse("LZ4 dictionary training: count is 0, there are no sample pages"), false;
+    if (count > TYCHE_LZ4_TRAIN_MAX_PAGES)
+        return train_refuse("LZ4 dictionary training: " + std::to_string(count) + " sample pages are more than TYCHE_LZ4_TRAIN_MAX_PAGES (" +
+                            std::to_string(TYCHE_LZ4_TRAIN_MAX_PAGES) + ")"), false;
+    return true;
+}
+std::nullptr_t train_page_too_long(const std::string &which, uint64_t len) {
+    return train_refuse("LZ4 dictionary training: " + which + " (" + std::to_string(len) + " bytes) is above 65535 bytes");
+}
+std::nullptr_t train_too_many_bytes(uint64_t total) {
+    return train_refuse("LZ4 dictionary training: the sample pages hold " + std::to_string(total) +
+                        " bytes, more than TYCHE_LZ4_TRAIN_MAX_BYTES (" + std::to_string(TYCHE_LZ4_TRAIN_MAX_BYTES) + ")");
+}
+// the batch is on the current device, its arguments checked
+tyche_lz4_dict *train_on_device(const tyche_batch_t &b, uint32_t in_cap, uint32_t dict_len, hipStream_t s) {
+    std::vector<uint8_t> bytes(dict_len);
+    TrainResult r;
+    const hipError_t e = train_lz4_dict(b, in_cap, dict_len, s, bytes.data(), &r);
+    if (e != hipSuccess) return fail((std::string("lz4 dictionary training (") + r.step + ")").c_str(), e), nullptr;
+    if (r.too_long)
+        return train_refuse("LZ4 dictionary training: a sample page is longer than the batch's declared maximum (" +
+                            std::to_string(in_cap) + " bytes; at most 65535)");
+    if (r.total_bytes > TYCHE_LZ4_TRAIN_MAX_BYTES) return train_too_many_bytes(r.total_bytes);
+    if (r.dict_len == 0)
+        return train_refuse("LZ4 dictionary training: the sample pages share no content (no 8-byte key occurs in two of the " +
+                            std::to_string(b.count) + " pages), so there is nothing to put into a dictionary");
+    return dict_create(bytes.data(), r.dict_len);
+}
+// n pages packed one after another in `data`
+tyche_lz4_dict *train_packed(const uint8_t *data, const uint32_t *lens, size_t n, uint32_t dict_len) {
+    DeviceGuard keep;
+    int dev = 0;
+    if (current_device(&dev) != TYCHE_E_OK || ensure_device(dev) != TYCHE_E_OK) return nullptr;
+    uint64_t total = 0;
+    uint32_t longest = 0;
+    std::vector<uint64_t> offs(n);
+    for (size_t i = 0; i < n; i++) {
+        offs[i] = total;
+        total += lens[i];
+        longest = std::max(longest, lens[i]);
+    }
+    const size_t data_bytes = ((size_t)total + 15u) & ~(size_t)15u, off_bytes = n * sizeof(uint64_t);
+    uint8_t *dm = nullptr;
+    hipError_t e = hipMalloc((void **)&dm, data_bytes + 16u + off_bytes + n * sizeof(uint32_t));
+    if (e != hipSuccess) return fail("hipMalloc(sample pages)", e), nullptr;
+    uint64_t *d_off = (uint64_t *)(dm + data_bytes + 16u);
+    uint32_t *d_len = (uint32_t *)(dm + data_bytes + 16u + off_bytes);
+    if ((total && (e = hipMemcpy(dm, data, (size_t)total, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (e = hipMemcpy(d_off, offs.data(), off_bytes, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(d_len, lens, n * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) {
+        (void)hipFree(dm);
+        return fail("hipMemcpy(sample pages)", e), nullptr;
+    }
+    tyche_batch_t b = {};
+    b.count = n;
+    b.src = dm;
+    b.src_offsets = d_off;
+    b.src_lengths = d_len;
+    b.max_src_length = longest;
+    tyche_lz4_dict *d = train_on_device(b, std::max(longest, 1u), dict_len, nullptr);
+    (void)hipFree(dm);
+    return d;
 }
 
 }  // namespace
@@ -1631,12 +1798,62 @@ int tyche_lz4_use_dict(const tyche_lz4_dict_t *d) {
         std::lock_guard<std::mutex> g(S.mu);
         S.env_done = true;   // an explicit choice replaces whatever TYCHE_LZ4_DICT names
         S.env_error.clear();
+        S.end_auto();        // and ends TYCHE_LZ4_DICT_AUTO: a training still running will not install
         old = S.d;
         if (d) dict_retain(d);
         S.d = d;
     }
     dict_release(old);
     return TYCHE_E_OK;
+}
+
+uint32_t tyche_lz4_dict_bytes(const tyche_lz4_dict_t *d, void *out, uint32_t cap) {
+    if (!d) return 0u;
+    if (out && cap) memcpy(out, d->image.data() + (d->dpad - d->len), std::min(cap, d->len));
+    return d->len;
+}
+
+tyche_lz4_dict_t *tyche_lz4_current_dict(void) {
+    DictSlot &S = dict_slot();
+    std::lock_guard<std::mutex> g(S.mu);
+    dict_env_locked(S);
+    if (S.d) dict_retain(S.d);
+    return const_cast<tyche_lz4_dict *>(S.d);
+}
+
+tyche_lz4_dict_t *tyche_lz4_dict_train_batch(const tyche_batch_t *samples, uint32_t dict_len, void *stream) {
+    if (!samples) return train_refuse("LZ4 dictionary training: samples is NULL");
+    if (!train_args_ok(dict_len, samples->count)) return nullptr;
+    if (!samples->src) return train_refuse("LZ4 dictionary training: samples->src is NULL");
+    uint32_t in_cap = samples->src_lengths ? samples->max_src_length : samples->src_length;
+    if (samples->src_lengths && in_cap == 0) in_cap = 65535;
+    if (in_cap > 65535u) return train_page_too_long(samples->src_lengths ? "the batch's declared maximum" : "src_length", in_cap);
+    if (!samples->src_lengths && (uint64_t)samples->count * in_cap > TYCHE_LZ4_TRAIN_MAX_BYTES)
+        return train_too_many_bytes((uint64_t)samples->count * in_cap);
+    DeviceGuard keep;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) return fail_msg("no HIP device available (the codec runs only on the GPU)"), nullptr;
+    if (stream_device((hipStream_t)stream)) return nullptr;
+    return train_on_device(*samples, std::max(in_cap, 1u), dict_len, (hipStream_t)stream);
+}
+
+tyche_lz4_dict_t *tyche_lz4_dict_train_host(size_t n, const void *const *src, const uint32_t *src_lengths,
+                                            uint32_t dict_len) {
+    if (!train_args_ok(dict_len, n)) return nullptr;
+    if (!src || !src_lengths) return train_refuse("LZ4 dictionary training: src or src_lengths is NULL");
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (src_lengths[i] > 65535u) return train_page_too_long("page " + std::to_string(i), src_lengths[i]);
+        total += src_lengths[i];
+    }
+    if (total > TYCHE_LZ4_TRAIN_MAX_BYTES) return train_too_many_bytes(total);
+    std::vector<uint8_t> data((size_t)total);
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (src_lengths[i]) memcpy(data.data() + at, src[i], src_lengths[i]);
+        at += src_lengths[i];
+    }
+    return train_packed(data.data(), src_lengths, n, dict_len);
 }
 
 int tyche_lz4_compress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream) {
@@ -1692,9 +1909,21 @@ int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const
     // the dictionary encoder; a chunk that also holds longer pages runs today's launch first, for
     // their bytes, and the dictionary launch then writes the pages in reach over it.
     DictHold dict;
+    AutoSample trained_from;   // TYCHE_LZ4_DICT_AUTO: the sample, when this call completed it
     if (compressor_id == TYCHE_LZ4_COMPRESSOR_ID) {
         if (int rc = dict_for_host_call(&dict.d)) return rc;
         if (dict.d && knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
+        if (!dict.d)
+            if (int rc = auto_collect(n, src, src_lengths, &trained_from)) return rc;
+    }
+    if (trained_from.dict_len) {
+        // compressed plain like every call before the install, then trained and installed
+        const int rc = run_host(n, src, src_lengths, dst, dst_capacities, results,
+                                [](const tyche_batch_t &b, hipStream_t s, bool) {
+                                    return launch_encode(TYCHE_LZ4_COMPRESSOR_ID, b, std::max(b.max_src_length, 1u), s);
+                                }, false, direct);
+        auto_train_and_install(trained_from);
+        return rc;
     }
     if (const tyche_lz4_dict *d = dict.d) {
         DictUploadNote note;
