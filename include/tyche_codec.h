@@ -160,6 +160,20 @@ int tyche_restore_queue_hist(uint64_t *counts, int n);
  * `stream` is a hipStream_t (NULL = default stream); the call is asynchronous. */
 #define TYCHE_LZ4_MAX_PAGE (4u << 20)   /* largest LZ4 page length and decode capacity */
 
+/* Batch contract.  For every page of a device or host batch, on every kernel
+ * path and in both directions: nothing outside [dst, dst + capacity) is
+ * written; the bytes in [result, capacity) are unspecified afterwards (a codec
+ * may use them as scratch); src is never written; no result and no output byte
+ * depends on a byte outside [src, src + length), although whole 16-byte lines
+ * around it may be read; and src and dst of every page may have any byte
+ * alignment.  A page above the launch's declared maximum (INT32_MIN) leaves its
+ * destination untouched.  For decompress that maximum is dst_capacity; a
+ * stream longer than the declared max_src_length also gives INT32_MIN from LZ4
+ * and zstd, while zlib inflate does not use the declared stream maximum and
+ * returns its verdict.  Held by tests/test_gpu_batch_contract.py on the checked
+ * layout of tests/batch_layout.py (guard bytes around every slot, chosen bytes
+ * around every source, every alignment), which the decode helpers of
+ * tests/test_gpu_lz4.py, test_gpu_zstd.py and test_gpu_zlib.py share. */
 typedef struct tyche_batch {
     size_t count;
     const void *src;

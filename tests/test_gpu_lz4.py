@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from batch_contract_cases import checked_decode
 from conftest import load_golden, unpack
 
 pytestmark = pytest.mark.gpu
@@ -31,35 +32,10 @@ def tc():
 
 
 def ragged_decode(tc, streams, caps):
-    """Decode a list of byte strings with per-page capacities through the general batch API."""
-    n = len(streams)
-    lens = [len(s) for s in streams]
-    offs = np.zeros(n, np.int64)
-    pos = 0
-    for i, s in enumerate(streams):
-        offs[i] = pos
-        pos += (len(s) + 15) // 16 * 16 + 16
-    buf = np.zeros(pos + 64, np.uint8)
-    for i, s in enumerate(streams):
-        buf[offs[i]:offs[i] + len(s)] = np.frombuffer(s, np.uint8)
-    ooffs = np.zeros(n, np.int64)
-    opos = 0
-    for i, c in enumerate(caps):
-        ooffs[i] = opos
-        opos += (c + 15) // 16 * 16 + 16
-    d_stream = torch.from_numpy(buf).to(DEV)
-    d_out = torch.full((opos + 64,), 0xAB, dtype=torch.uint8, device=DEV)
-    d_offs = torch.from_numpy(offs.astype(np.uint64).view(np.int64)).to(DEV)
-    d_lens = torch.tensor(lens, dtype=torch.int32, device=DEV)
-    d_caps = torch.tensor(caps, dtype=torch.int32, device=DEV)
-    d_ooffs = torch.from_numpy(ooffs).to(DEV)
-    d_rv = torch.empty(n, dtype=torch.int32, device=DEV)
-    tc.decompress_ragged(d_stream, d_offs, d_lens, d_caps, d_out, d_ooffs, d_rv,
-                         max_src_length=max(lens + [1]), max_capacity=max(caps + [0]))
-    torch.cuda.synchronize()
-    rv = d_rv.cpu().numpy()
-    out = d_out.cpu().numpy()
-    return rv, [out[ooffs[i]:ooffs[i] + max(int(rv[i]), 0)].tobytes() for i in range(n)]
+    """Decode a list of byte strings with per-page capacities through the general batch API, on the
+    checked layout (batch_layout.py): 64 guard bytes around every output slot and the stream arena
+    are compared after the run, so a byte written outside a slot fails whatever test called this."""
+    return checked_decode(tc, 1, streams, caps)
 
 
 def test_decode_kat(tc):

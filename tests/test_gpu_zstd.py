@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+from batch_contract_cases import checked_decode
 from conftest import load_golden, unpack
 
 pytestmark = pytest.mark.gpu
@@ -52,35 +53,10 @@ def tc():
 
 
 def ragged_decode(tc, streams, caps, shift=0, codec_id=ZSTD):
-    """Decode byte strings (each placed at a 16-byte boundary + shift) into per-page capacities."""
-    n = len(streams)
-    lens = [len(s) for s in streams]
-    offs = np.zeros(n, np.int64)
-    pos = 0
-    for i, s in enumerate(streams):
-        offs[i] = pos + shift
-        pos += (len(s) + shift + 15) // 16 * 16 + 16
-    buf = np.zeros(pos + 64, np.uint8)
-    for i, s in enumerate(streams):
-        buf[offs[i]:offs[i] + len(s)] = np.frombuffer(s, np.uint8)
-    ooffs = np.zeros(n, np.int64)
-    opos = 0
-    for i, c in enumerate(caps):
-        ooffs[i] = opos
-        opos += (c + 15) // 16 * 16 + 16
-    d_stream = torch.from_numpy(buf).to(DEV)
-    d_out = torch.full((opos + 64,), 0xAB, dtype=torch.uint8, device=DEV)
-    d_offs = torch.from_numpy(offs).to(DEV)
-    d_lens = torch.tensor(lens, dtype=torch.int32, device=DEV)
-    d_caps = torch.tensor(caps, dtype=torch.int32, device=DEV)
-    d_ooffs = torch.from_numpy(ooffs).to(DEV)
-    d_rv = torch.empty(n, dtype=torch.int32, device=DEV)
-    tc.decompress_ragged(d_stream, d_offs, d_lens, d_caps, d_out, d_ooffs, d_rv,
-                         max_src_length=max(lens + [1]), max_capacity=max(caps + [0]), compressor_id=codec_id)
-    torch.cuda.synchronize()
-    rv = d_rv.cpu().numpy()
-    out = d_out.cpu().numpy()
-    return rv, [out[ooffs[i]:ooffs[i] + max(int(rv[i]), 0)].tobytes() for i in range(n)]
+    """Decode byte strings (each placed at a 16-byte boundary + shift) into per-page capacities, on
+    the checked layout (batch_layout.py): 64 guard bytes around every output slot and the frame arena
+    are compared after the run, so a byte written outside a slot fails whatever test called this."""
+    return checked_decode(tc, codec_id, streams, caps, shift)
 
 
 def test_zstd_kat(tc):
@@ -480,6 +456,7 @@ def test_encode_tight_capacity(tc, oracle_mod, slack):
                "compress")
     torch.cuda.synchronize()
     ch, lh, host = comp2.cpu().numpy(), clen2.cpu().numpy(), pages.cpu().numpy()
+    assert not ch[:, cap:].any()      # nothing at or past the capacity was written (the slot was zeroed)
     for i in range(n):
         assert 0 <= lh[i] <= cap
         if lh[i] == 0:

@@ -1225,7 +1225,7 @@ __global__ __launch_bounds__(kJumpThreads) void lz4_decode_jump_kernel(tyche_bat
                 const uint32_t base = 16u * g;
                 if (al && base + 16u <= (uint32_t)rv) {
                     __builtin_nontemporal_store(o, (u32x4 *)(dst + base));
-                } else {
+                } else if (base < (uint32_t)rv) {   // (the groups of the last 64-cell chunk past rv write nothing)
                     const uint32_t n = min(16u, (uint32_t)rv - base);
                     for (uint32_t j = 0; j < n; j++) dst[base + j] = (uint8_t)(o[j >> 2] >> (8u * (j & 3u)));
                 }
