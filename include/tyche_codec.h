@@ -355,6 +355,27 @@ size_t tyche_plan_split(size_t n, const uint32_t *src_lengths, int ndev, uint64_
  * reference's byU16 regime only: with the knob on, an LZ4 compress launch whose
  * declared maximum (or a host page) exceeds 65535 bytes fails with
  * TYCHE_E_BAD_ARGS instead of being given another encoder's bytes.
+ * A fifth, LZ4_HC (default 0), sends every LZ4 compress launch -- the batch and
+ * host calls, buffer__compress, tyche_buffers_compress, the multi-device
+ * fan-out -- to the high-compression encoder for its pages of up to 65535
+ * bytes: the same LZ4 block format from a better parse (8 candidates per
+ * position and a lazy choice), so every decoder restores the streams unchanged.
+ * The batch contract is the default encoder's: results[i] is the size, or 0
+ * when the stream does not fit dst_capacity; nothing at or past dst +
+ * dst_capacity is written; src_len == 0 gives the block 0x00; INT32_MIN above
+ * the launch's maximum; a stream is never longer than tyche_compress_bound; the
+ * bytes depend on the page alone.  It changes the bytes, the ratio (11-20 %
+ * fewer bytes on the 16 KiB bench pages) and the time (about 23x the default
+ * encoder's at 16 KiB pages, 10x at 4 KiB), never the decode result.  It is a
+ * ratio mode, not a byte promise, so unlike LZ4_EXACT it never makes a launch
+ * fail: pages above 65535 bytes keep the large-page encoder and the bytes they
+ * have without the knob, also in a launch that mixes sizes.  LZ4_EXACT=1
+ * together with LZ4_HC=1 is TYCHE_E_BAD_ARGS from every LZ4 compress call (they
+ * contradict each other; tyche_last_error() says so).  A dictionary wins where
+ * it reaches: tyche_lz4_compress_batch_dict ignores the knob; with a
+ * process-wide dictionary the pages it reaches take the dictionary encoder as
+ * without the knob and the others take HC; while TYCHE_LZ4_DICT_AUTO collects
+ * its sample, plain pages take HC.  zlib and zstd ignore the knob.
  * Two are test hooks: FAIL_COMPRESS_EVERY=N fails every Nth compress launch
  * (TYCHE_E_DEVICE, the device-failure test) and LOG_ERRORS=1 prints engine
  * errors to stderr. */

@@ -15,6 +15,15 @@ become one standard LZ4 block each.  zlib and zstd compress rows of up to
 65,535 bytes, and so does LZ4 under ``LZ4_EXACT=1``; beyond a limit the call
 raises ``DeviceError`` (``TYCHE_E_BAD_ARGS``, the limit in the message).
 
+High-compression mode (LZ4 only): with ``TYCHE_LZ4_HC=1`` in the environment, or
+``_lib.set_knob("LZ4_HC", 1)``, ``compress_pages`` / ``compress_ragged`` give
+rows of up to 65,535 bytes to the high-compression encoder: the same LZ4 blocks
+from a better parse, 11-20 % fewer bytes on the 16 KiB bench pages at about 23x
+the default encoder's time, restored by ``decompress_pages`` as any other block
+(a little faster: fewer sequences).  Longer rows and ``dictionary=`` calls are
+as without the knob; ``LZ4_EXACT=1`` beside it raises ``DeviceError``
+(``TYCHE_E_BAD_ARGS``).
+
 Shared dictionary (LZ4 only): ``dictionary=Lz4Dict(bytes)`` makes the dictionary
 and each row one LZ4 window -- the blocks are what
 ``LZ4_decompress_safe_usingDict`` restores, and need the same dictionary to be

@@ -80,6 +80,11 @@ hipError_t launch_lz4_decode_lc(const tyche_batch_t &b, uint32_t in_cap, uint32_
 hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 // LZ4_EXACT=1: the bytes and return value of LZ4 1.7.5's LZ4_compress_default (lz4_encode_exact.hip)
 hipError_t launch_lz4_encode_exact(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
+// LZ4_HC=1: the same block format from a better parse -- 8-way bucket rings in LDS and a two-step lazy
+// choice, one wave per page (lz4_encode_hc.hip; in_cap <= 65535).  64K x 16 KiB bench pages: ratio 3.053
+// against 2.618, 86.2 ms against the default encoder's 3.8 ms and LZ4_EXACT's 53.7 ms; the decoders restore
+// its streams unchanged, in 0.86x the time (profiles/lz4_hc_time.log).
+hipError_t launch_lz4_encode_hc(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 // pages above 65,535 bytes, up to TYCHE_LZ4_MAX_PAGE (lz4_encode_large.hip): the pages of at least min_len
 // bytes; the results of shorter ones are left alone
 hipError_t launch_lz4_encode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t min_len, hipStream_t s);

@@ -500,8 +500,14 @@ hipError_t launch_encode(int id, const tyche_batch_t &b, uint32_t in_cap, hipStr
 // The largest page a compress launch may declare (and a host page may have): TYCHE_LZ4_MAX_PAGE
 // for LZ4, whose large-page encoder takes over above 65,535 bytes; 65,535 for zlib and zstd
 // (16-bit positions in their parses) and for LZ4 under LZ4_EXACT=1, which promises the reference's
-// byU16 bytes and is never quietly given another encoder's.
+// byU16 bytes and is never quietly given another encoder's.  Also where an LZ4 compress call with both
+// LZ4_EXACT=1 and LZ4_HC=1 is refused, before any device work.
 int check_page_limit(int id, uint32_t len) {
+    if (id == TYCHE_LZ4_COMPRESSOR_ID && knob("LZ4_EXACT", 0) != 0 && knob("LZ4_HC", 0) != 0) {
+        t_error = "LZ4_EXACT=1 and LZ4_HC=1 contradict each other: exact mode promises LZ4_compress_default's bytes, "
+                  "HC mode another parse's";
+        return TYCHE_E_BAD_ARGS;
+    }
     if (len <= 65535u) return TYCHE_E_OK;
     if (id == TYCHE_LZ4_COMPRESSOR_ID) {
         if (knob("LZ4_EXACT", 0) != 0) {

@@ -977,6 +977,10 @@ hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_
     }
     // TYCHE_LZ4_EXACT=1: every launch to the exact encoder (LZ4 1.7.5's bytes, lz4_encode_exact.hip)
     if (knob("LZ4_EXACT", 0) != 0) return launch_lz4_encode_exact(b, in_cap, s);
+    // TYCHE_LZ4_HC=1: every launch to the high-compression encoder (lz4_encode_hc.hip).  A launch with longer
+    // pages arrives here through the recursion above for its pages of up to 65,535 bytes: a ratio mode, not a
+    // byte promise, so the longer ones keep the large-page encoder.  (Both knobs set: refused by the entry points.)
+    if (knob("LZ4_HC", 0) != 0) return launch_lz4_encode_hc(b, in_cap, s);
     // TYCHE_LZ4_ENC=1: the one-wave kernel for every batch (A/B timing)
     const bool one_wave = knob("LZ4_ENC", 0) == 1;
     // waves per page of the split encoders (2: the two-wave kernel; 3 in round 3: 79.4 vs 85.0 ms per
