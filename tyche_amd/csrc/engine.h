@@ -1,5 +1,7 @@
 // engine.h -- internal interface between the C-ABI layer (engine.hip) and the
-// gfx950 kernels (lz4_decode.hip, lz4_encode.hip, pagegen.hip).
+// gfx950 kernel files (the lz4_*, zlib_* and zstd_* .hip files, pagegen.hip):
+// their launchers, the batch's page metadata, and the launch plumbing they
+// share -- grid sizing, dynamic page assignment, scratch leases, knobs.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -58,16 +60,20 @@ __device__ inline PageRef batch_page(const tyche_batch_t &b, size_t i) {
 // barrier is all that is required.
 #define WAVE_SYNC() __builtin_amdgcn_wave_barrier()
 
-// Resident one-wave workgroups per CU for a kernel at `lds` bytes of dynamic
-// LDS, as the runtime computes it (LDS granules, VGPRs, the per-CU limits).
-// The page loops size their grids to exactly this: one more workgroup per CU
-// than fits would run after a resident one finished its whole share of pages.
-inline size_t waves_per_cu(const void *kernel, size_t lds) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 64, lds) == hipSuccess && n > 0) return (size_t)n;
-    const size_t granted = (lds + 511u) & ~(size_t)511u;
-    return granted ? std::max<size_t>(1, std::min<size_t>(32, (160 * 1024) / granted)) : 32;
-}
+// Resident workgroups of `threads` threads per CU for a kernel at `lds` bytes
+// of dynamic LDS, as the runtime computes it (LDS granules, VGPRs, the per-CU
+// limits).  The page loops size their grids to exactly this: one more workgroup
+// per CU than fits would run after a resident one finished its whole share of
+// pages.  If the runtime gives no answer: what the LDS allows for one-wave
+// workgroups, 1 for larger ones.
+size_t blocks_per_cu(const void *kernel, uint32_t threads, size_t lds);
+// The grid of a page-loop launch over `count` pages: prepare_launch, then
+// min(count, CUs x blocks_per_cu), the blocks per CU capped by the knob
+// `cap_knob` (a *_PAGES_PER_CU name; a literal, as knob() wants) when it is
+// set above 0.  The grid claims pages when it is smaller than count.  A batch of
+// no more pages than CUs takes one workgroup per page whatever fits, so the
+// occupancy is not asked for: the restore path pays no host call here.
+size_t page_grid(const void *kernel, uint32_t threads, size_t lds, size_t count, const char *cap_knob = nullptr);
 
 hipError_t launch_lz4_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s,
                              bool allow_lane = true);

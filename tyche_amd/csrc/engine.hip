@@ -282,6 +282,23 @@ size_t tyche::prepare_launch(const void *kernel) {
     return (size_t)cus[dev];
 }
 
+size_t tyche::blocks_per_cu(const void *kernel, uint32_t threads, size_t lds) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, (int)threads, lds) == hipSuccess && n > 0) return (size_t)n;
+    if (threads != 64) return 1;
+    const size_t granted = (lds + 511u) & ~(size_t)511u;
+    return granted ? std::max<size_t>(1, std::min<size_t>(32, (160 * 1024) / granted)) : 32;
+}
+
+size_t tyche::page_grid(const void *kernel, uint32_t threads, size_t lds, size_t count, const char *cap_knob) {
+    const size_t ncu = prepare_launch(kernel);
+    if (count <= ncu) return count;
+    size_t per_cu = blocks_per_cu(kernel, threads, lds);
+    const long cap_cu = cap_knob ? knob(cap_knob, 0) : 0;   // (occupancy A/B: resident pages per CU; 0: what fits)
+    if (cap_cu > 0) per_cu = std::min<size_t>(per_cu, (size_t)cap_cu);
+    return std::min<size_t>(count, ncu * per_cu);
+}
+
 namespace {
 struct KnobTable {
     std::mutex mu;
@@ -476,7 +493,7 @@ int current_device(int *dev) {
     return TYCHE_E_OK;
 }
 
-// codecs with a gfx950 kernel, per direction
+// codecs with a gfx950 kernel (all of them have one in both directions)
 bool valid_codec(int id) {
     return id == TYCHE_LZ4_COMPRESSOR_ID || id == TYCHE_ZLIB_COMPRESSOR_ID || id == TYCHE_ZSTD_COMPRESSOR_ID;
 }
@@ -521,9 +538,6 @@ int check_page_limit(int id, uint32_t len) {
     t_error = std::string(id == TYCHE_ZSTD_COMPRESSOR_ID ? "zstd" : "zlib") + " pages above 65535 bytes are not supported";
     return TYCHE_E_BAD_ARGS;
 }
-bool valid_decode_codec(int id) {
-    return id == TYCHE_LZ4_COMPRESSOR_ID || id == TYCHE_ZLIB_COMPRESSOR_ID || id == TYCHE_ZSTD_COMPRESSOR_ID;
-}
 
 std::string codec_msg(int id) {
     if (id == TYCHE_ZLIB_COMPRESSOR_ID || id == TYCHE_ZSTD_COMPRESSOR_ID)
@@ -542,6 +556,8 @@ inline uint32_t decode_in_cap(const tyche_batch_t &b, uint32_t fallback) {
     if (b.src_lengths && in_cap == 0) in_cap = fallback;
     return in_cap;
 }
+// in_cap for an encode batch: the largest page length, 65,535 when per-page lengths come without a maximum
+inline uint32_t encode_in_cap(const tyche_batch_t &b) { return decode_in_cap(b, 65535u); }
 
 // ---------------------------------------------------------------- host batches
 // The Buffer API and the host batch entry points start and end in host memory
@@ -1750,8 +1766,7 @@ int tyche_compress_batch(int compressor_id, int compressor_level, const tyche_ba
     if (!valid_codec(compressor_id)) { t_error = codec_msg(compressor_id); return TYCHE_E_BAD_ARGS; }
     if (batch->count == 0) return TYCHE_E_OK;
     if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
-    uint32_t in_cap = batch->src_lengths ? batch->max_src_length : batch->src_length;
-    if (batch->src_lengths && in_cap == 0) in_cap = 65535;
+    const uint32_t in_cap = encode_in_cap(*batch);
     if (int rc = check_page_limit(compressor_id, in_cap)) return rc;
     DeviceGuard keep;
     if (int rc = stream_device((hipStream_t)stream)) return rc;
@@ -1762,7 +1777,7 @@ int tyche_compress_batch(int compressor_id, int compressor_level, const tyche_ba
 
 int tyche_decompress_batch(int compressor_id, const tyche_batch_t *batch, void *stream) {
     if (!batch) return TYCHE_E_BAD_ARGS;
-    if (!valid_decode_codec(compressor_id)) { t_error = codec_msg(compressor_id); return TYCHE_E_BAD_ARGS; }
+    if (!valid_codec(compressor_id)) { t_error = codec_msg(compressor_id); return TYCHE_E_BAD_ARGS; }
     if (batch->count == 0) return TYCHE_E_OK;
     if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
     DeviceGuard keep;
@@ -1831,8 +1846,7 @@ tyche_lz4_dict_t *tyche_lz4_dict_train_batch(const tyche_batch_t *samples, uint3
     if (!samples) return train_refuse("LZ4 dictionary training: samples is NULL");
     if (!train_args_ok(dict_len, samples->count)) return nullptr;
     if (!samples->src) return train_refuse("LZ4 dictionary training: samples->src is NULL");
-    uint32_t in_cap = samples->src_lengths ? samples->max_src_length : samples->src_length;
-    if (samples->src_lengths && in_cap == 0) in_cap = 65535;
+    const uint32_t in_cap = encode_in_cap(*samples);
     if (in_cap > 65535u) return train_page_too_long(samples->src_lengths ? "the batch's declared maximum" : "src_length", in_cap);
     if (!samples->src_lengths && (uint64_t)samples->count * in_cap > TYCHE_LZ4_TRAIN_MAX_BYTES)
         return train_too_many_bytes((uint64_t)samples->count * in_cap);
@@ -1867,8 +1881,7 @@ int tyche_lz4_compress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t
     if (knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
     if (batch->count == 0) return TYCHE_E_OK;
     if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
-    uint32_t in_cap = batch->src_lengths ? batch->max_src_length : batch->src_length;
-    if (batch->src_lengths && in_cap == 0) in_cap = 65535;
+    const uint32_t in_cap = encode_in_cap(*batch);
     if ((uint64_t)in_cap + d->len > 65536u) return dict_reach_error("the launch's largest page", in_cap, d->len);
     DeviceGuard keep;
     if (int rc = stream_device((hipStream_t)stream)) return rc;
@@ -1954,7 +1967,7 @@ int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const
 
 int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, const uint32_t *src_lengths,
                           void *const *dst, const uint32_t *dst_capacities, int32_t *results) {
-    if (!valid_decode_codec(compressor_id)) { t_error = codec_msg(compressor_id); return TYCHE_E_BAD_ARGS; }
+    if (!valid_codec(compressor_id)) { t_error = codec_msg(compressor_id); return TYCHE_E_BAD_ARGS; }
     if (n == 0) return TYCHE_E_OK;
     if (compressor_id == TYCHE_ZLIB_COMPRESSOR_ID)
         return run_host(n, src, src_lengths, dst, dst_capacities, results,
@@ -2155,10 +2168,10 @@ int tyche_buffers_decompress(Buffer **bufs, int *status, size_t n, int compresso
     for (size_t i = 0; i < n; i++) {
         status[i] = decompress_precheck(bufs[i], compressor_id);
         if (status[i] == -1) {
-            if (!valid_decode_codec(compressor_id) && compressor_id >= 1 && compressor_id <= 3) {
+            if (!valid_codec(compressor_id) && compressor_id >= 1 && compressor_id <= 3) {
                 t_error = codec_msg(compressor_id);
                 status[i] = TYCHE_E_BUFFER_COMPRESSION_PROBLEM;
-            } else if (!valid_decode_codec(compressor_id)) {
+            } else if (!valid_codec(compressor_id)) {
                 // unknown id: the reference swaps in an unfilled malloc(data_length) block and
                 // reports success (buffer.c:244-279); mirrored, with the block zeroed.
                 Buffer *b = bufs[i];

@@ -93,6 +93,48 @@ __device__ __forceinline__ uint32_t stage_in(const uint8_t *src, uint32_t n, uin
     return head;
 }
 
+// The next page of a page-loop kernel, on its way into the stage: its first
+// kVec 16-byte vectors per thread (kVec * kThreads * 16 bytes) wait in registers
+// while the kernel works on the current page in that stage.
+//   TYCHE_NEXT_PAGE(kVec)        declares the registers pf[], and nhead = nvec = 0
+//   TYCHE_NEXT_PAGE_FETCH(...)   issues the loads for a page of len bytes at src;
+//                                an empty page or one above in_cap: nothing
+//   TYCHE_NEXT_PAGE_INSTALL(...) writes them where stage_in would have (byte j of
+//                                src at stage[nhead + j]) and loads what lies
+//                                past the register window
+// Which page is next, what happens in between, the barriers around the install
+// and `head = nhead` are the kernel's.  These are fragments expanded in the
+// kernel, not functions of a struct: as members (a struct holding pf[], head and
+// nvec) the same statements compiled to other register counts in nearly every
+// kernel and to measurably other times -- the array's run-time index keeps the
+// whole object, its two scalars included, in memory until the loops are unrolled,
+// and a member is simplified on its own before it is inlined
+// (profiles/page_loop_resources.md).
+#define TYCHE_NEXT_PAGE(kVec) \
+    u32x4 pf[kVec];           \
+    uint32_t nhead = 0, nvec = 0
+#define TYCHE_NEXT_PAGE_FETCH(kVec, kThreads, src, len, in_cap, tid)                                       \
+    if ((len) <= (in_cap) && (len) > 0) {                                                                  \
+        const uintptr_t a_ = (uintptr_t)(src);                                                             \
+        nhead = (uint32_t)(a_ & 15u);                                                                      \
+        nvec = (nhead + (len) + 15u) >> 4;                                                                 \
+        const u32x4 *g_ = (const u32x4 *)(a_ - nhead);                                                     \
+        _Pragma("unroll") for (uint32_t k_ = 0; k_ < (kVec); k_++) {                                       \
+            const uint32_t v_ = (tid) + k_ * (kThreads);                                                   \
+            pf[k_] = gload_nt(g_ + min(v_, nvec - 1u)); /* clamped: no branch, always in bounds */         \
+        }                                                                                                  \
+    }
+#define TYCHE_NEXT_PAGE_INSTALL(kVec, kThreads, src, len, in_cap, stage, tid)                              \
+    if ((len) <= (in_cap) && (len) > 0) {                                                                  \
+        u32x4 *l_ = (u32x4 *)(stage);                                                                      \
+        _Pragma("unroll") for (uint32_t k_ = 0; k_ < (kVec); k_++) {                                       \
+            const uint32_t v_ = (tid) + k_ * (kThreads);                                                   \
+            if (v_ < nvec) l_[v_] = pf[k_];                                                                \
+        }                                                                                                  \
+        const u32x4 *g_ = (const u32x4 *)((uintptr_t)(src) - nhead);                                       \
+        for (uint32_t v_ = (tid) + (kVec) * (kThreads); v_ < nvec; v_ += (kThreads)) l_[v_] = gload_nt(g_ + v_); \
+    }
+
 // Writes n bytes from LDS (lds, 16-byte aligned base, data starting at lds[0])
 // to global dst (any alignment).  Aligned destinations use 16-byte stores.
 __device__ __forceinline__ void stage_out(uint8_t *dst, const uint8_t *lds, uint32_t n, uint32_t tid,

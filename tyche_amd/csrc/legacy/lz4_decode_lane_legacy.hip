@@ -611,7 +611,7 @@ hipError_t launch_lz4_decode_lane_legacy(const tyche_batch_t &b, uint32_t in_cap
         const int32_t rbytes = ring == 128 ? 128 : ring == 160 ? 160 : ring == 192 ? 192 : ring == 224 ? 224 : 256;
         const size_t lds = 64 * (size_t)(rbytes + 48 + 80);
         const size_t ncu = prepare_launch(k);
-        size_t waves = waves_per_cu(k, lds);
+        size_t waves = blocks_per_cu(k, 64, lds);
         if (env_waves > 0) waves = std::min<size_t>(waves, (size_t)env_waves);
         const size_t grid = std::min<size_t>((b.count + 63) / 64, ncu * waves);
         WorkCounter ctr(s, grid * 64 < b.count);
@@ -632,7 +632,7 @@ hipError_t launch_lz4_decode_lane_legacy(const tyche_batch_t &b, uint32_t in_cap
         const int32_t rbytes = ring == 128 ? 128 : ring == 256 ? 256 : 512;
         const size_t lds = 64 * (size_t)(rbytes + 48);
         const size_t ncu = prepare_launch(k);
-        size_t waves = waves_per_cu(k, lds);
+        size_t waves = blocks_per_cu(k, 64, lds);
         if (env_waves > 0) waves = std::min<size_t>(waves, (size_t)env_waves);
         const size_t grid = std::min<size_t>((b.count + 63) / 64, ncu * waves);
         WorkCounter ctr(s, grid * 64 < b.count);
@@ -643,7 +643,7 @@ hipError_t launch_lz4_decode_lane_legacy(const tyche_batch_t &b, uint32_t in_cap
         return hipGetLastError();
     }
     const size_t ncu = prepare_launch((const void *)lz4_decode_lane_kernel);
-    size_t waves = waves_per_cu((const void *)lz4_decode_lane_kernel, 0);
+    size_t waves = blocks_per_cu((const void *)lz4_decode_lane_kernel, 64, 0);
     waves = std::min<size_t>(waves, env_waves > 0 ? (size_t)env_waves : kLaneWaves);
     const size_t grid = std::min<size_t>((b.count + 63) / 64, ncu * waves);
     WorkCounter ctr(s, grid * 64 < b.count);

@@ -651,7 +651,7 @@ hipError_t launch_lz4_decode_quad(const tyche_batch_t &b, uint32_t in_cap, uint3
         lds = QL<1024, 8>::total;
     }
     const size_t ncu = prepare_launch(k);
-    size_t waves = waves_per_cu(k, lds);
+    size_t waves = blocks_per_cu(k, 64, lds);
     const long env_waves = knob("LZ4_QUAD_WAVES", 0);
     if (env_waves > 0) waves = std::min<size_t>(waves, (size_t)env_waves);
     const size_t grid = std::min<size_t>((b.count + 15) / 16, ncu * waves);

@@ -585,21 +585,10 @@ __global__ __launch_bounds__(64) void lz4_decode_wave_kernel(tyche_batch_t b, ui
                                 : next_in_class(b, page + stride, stride, cls_lo, cls_hi);
         // ---- prefetch the next page's stream (first 8 KiB) into registers
         PageRef pn;
-        u32x4 pf[kPrefetchVec];
-        uint32_t nhead = 0, nvec = 0;
+        TYCHE_NEXT_PAGE(kPrefetchVec);
         if (next < b.count) {
             pn = batch_page(b, next);
-            if (pn.src_len <= in_cap && pn.src_len > 0) {
-                uintptr_t a = (uintptr_t)pn.src;
-                nhead = (uint32_t)(a & 15u);
-                nvec = (nhead + pn.src_len + 15u) >> 4;
-                const u32x4 *g = (const u32x4 *)(a - nhead);
-#pragma unroll
-                for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                    const uint32_t v = lane + k * kWave;
-                    pf[k] = gload_nt(g + min(v, nvec - 1u));   // clamped: no branch, always in bounds
-                }
-            }
+            TYCHE_NEXT_PAGE_FETCH(kPrefetchVec, kWave, pn.src, pn.src_len, in_cap, lane)
         }
         // ---- current page
         int32_t rv;
@@ -624,16 +613,7 @@ __global__ __launch_bounds__(64) void lz4_decode_wave_kernel(tyche_batch_t b, ui
         page = next;
         p = pn;
         head = nhead;
-        if (p.src_len <= in_cap && p.src_len > 0) {
-            u32x4 *l = (u32x4 *)stage;
-#pragma unroll
-            for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                const uint32_t v = lane + k * kWave;
-                if (v < nvec) l[v] = pf[k];
-            }
-            const u32x4 *g = (const u32x4 *)((uintptr_t)p.src - nhead);
-            for (uint32_t v = lane + kPrefetchVec * kWave; v < nvec; v += kWave) l[v] = gload_nt(g + v);
-        }
+        TYCHE_NEXT_PAGE_INSTALL(kPrefetchVec, kWave, p.src, p.src_len, in_cap, stage, lane)
         PROF_MARK(12);
     }
 }
@@ -1808,11 +1788,9 @@ static hipError_t launch_lz4_decode_jump(const tyche_batch_t &b, uint32_t in_cap
     const bool wide = wide_env && b.count <= ncu;
     const void *k = wide ? k1024 : k512;
     const uint32_t threads = wide ? 1024u : 512u;
+    // (two kernels sized against one CU count: the wide one only ever runs one workgroup per page)
     if (wide) (void)prepare_launch(k1024);
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, (int)threads, lds) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-    const size_t grid = std::min<size_t>(b.count, ncu * (size_t)per_cu);
+    const size_t grid = b.count <= ncu ? b.count : std::min<size_t>(b.count, ncu * blocks_per_cu(k, threads, lds));
     WorkCounter ctr(s, grid < b.count);
     if (grid < b.count && !ctr.get()) return hipErrorOutOfMemory;
     unsigned *cp = grid < b.count ? ctr.get() : nullptr;
@@ -1835,12 +1813,7 @@ static hipError_t launch_lz4_decode_solo(const tyche_batch_t &b, uint32_t in_cap
     const SoloLay lay = solo_layout(in_cap, out_cap);
     if (lay.total > 160u * 1024u) return hipSuccess;
     const void *k = (const void *)lz4_decode_solo_kernel<kT>;
-    const size_t ncu = prepare_launch(k);
-    int per_cu = 1;   // (batches up to one page per CU -- the restore path's -- skip the occupancy query)
-    if (b.count > ncu &&
-        (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, (int)kT, lay.total) != hipSuccess || per_cu < 1))
-        per_cu = 1;
-    const size_t grid = std::min<size_t>(b.count, ncu * (size_t)per_cu);
+    const size_t grid = page_grid(k, kT, lay.total, b.count);   // (the restore path's batches, up to a page per CU: no occupancy query)
     WorkCounter ctr(s, grid < b.count);
     if (grid < b.count && !ctr.get()) return hipErrorOutOfMemory;
     unsigned *cp = grid < b.count ? ctr.get() : nullptr;
@@ -1900,7 +1873,7 @@ hipError_t launch_lz4_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t o
     auto launch = [&](uint32_t cap, uint32_t lo, uint32_t hi, uint32_t chunk) -> hipError_t {
         const size_t l = lds_for(cap);
         const uint32_t win = (std::max(out_cap, cap + 4u) + 16u + 15u) & ~15u;
-        const size_t per_cu = waves_per_cu((const void *)lz4_decode_wave_kernel, l);
+        const size_t per_cu = blocks_per_cu((const void *)lz4_decode_wave_kernel, 64, l);
         const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
         WorkCounter ctr(s, grid < b.count);
         if (chunk && !ctr.get()) return hipErrorOutOfMemory;
@@ -1924,13 +1897,13 @@ hipError_t launch_lz4_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t o
     constexpr uint32_t kClassChunk = TYCHE_CLASS_CHUNK;   // static striding when 0
     const long split_env = knob("DECODE_CLASSES", 1);
     const size_t waves = split_env && b.src_lengths && b.count >= 8192
-                             ? waves_per_cu((const void *)lz4_decode_wave_kernel, lds) : 32;
+                             ? blocks_per_cu((const void *)lz4_decode_wave_kernel, 64, lds) : 32;
     if (waves < 16) {
         const size_t target = (160 * 1024) / (waves + 1);
         uint32_t T = in_cap;
         while (T > 16u && granted(lds_for(T)) > target) T -= 16u;
         if (granted(lds_for(T)) <= target && T >= in_cap / 2u && T < in_cap &&
-            waves_per_cu((const void *)lz4_decode_wave_kernel, lds_for(T)) > waves) {
+            blocks_per_cu((const void *)lz4_decode_wave_kernel, 64, lds_for(T)) > waves) {
             hipError_t e = launch(T, 0u, T, 1u);
             if (e != hipSuccess) return e;
             return launch(in_cap, T + 1u, 0xFFFFFFFFu, kClassChunk);

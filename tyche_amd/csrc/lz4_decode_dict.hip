@@ -75,9 +75,7 @@ hipError_t launch_lz4_decode_dict(const tyche_batch_t &b, uint32_t in_cap, uint3
     if ((uint64_t)out_cap + d.dlen > lzd::kWindowMax || d.dpad < d.dlen || (d.dpad & 15u)) return hipErrorInvalidValue;
     const size_t lds = d.dpad + ((out_cap + 15u) & ~15u) + ((in_cap + 16u + kPadD + 15u) & ~15u);
     if (lds > 160u * 1024u) return hipErrorInvalidValue;   // (a declared stream maximum beyond any the window can need)
-    const size_t ncu = prepare_launch((const void *)lz4_decode_dict_kernel);
-    const size_t per_cu = waves_per_cu((const void *)lz4_decode_dict_kernel, lds);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)lz4_decode_dict_kernel, kWaveD, lds, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(lz4_decode_dict_kernel, dim3((unsigned)grid), dim3(kWaveD), lds, s, b, in_cap, out_cap, d,

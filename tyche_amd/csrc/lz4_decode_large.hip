@@ -53,9 +53,7 @@ __global__ __launch_bounds__(64) void lz4_decode_large_kernel(tyche_batch_t b, u
 hipError_t launch_lz4_decode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s) {
     if (b.count == 0) return hipSuccess;
     if (out_cap > TYCHE_LZ4_MAX_PAGE || in_cap > lz4_bound(TYCHE_LZ4_MAX_PAGE)) return hipErrorInvalidValue;
-    const size_t ncu = prepare_launch((const void *)lz4_decode_large_kernel);
-    const size_t per_cu = waves_per_cu((const void *)lz4_decode_large_kernel, kDecLargeLds);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)lz4_decode_large_kernel, 64, kDecLargeLds, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(lz4_decode_large_kernel, dim3((unsigned)grid), dim3(64), kDecLargeLds, s, b, in_cap, out_cap,

@@ -491,7 +491,7 @@ hipError_t launch_lz4_decode_lc(const tyche_batch_t &b, uint32_t in_cap, uint32_
     const size_t lds = r == 256 ? LCL<256>::total : LCL<192>::total;
 #endif
     const size_t ncu = prepare_launch(k);
-    size_t waves = waves_per_cu(k, lds);
+    size_t waves = blocks_per_cu(k, 64, lds);
     const long env_waves = knob("LZ4_LC_WAVES", 8);   // (LC_FAR16's 154 VGPRs would allow more at R = 128 / 160: slower)
     if (env_waves > 0) waves = std::min<size_t>(waves, (size_t)env_waves);
     const size_t grid = std::min<size_t>((b.count + 63) / 64, ncu * waves);

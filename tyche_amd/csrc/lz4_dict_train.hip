@@ -155,12 +155,6 @@ __global__ __launch_bounds__(lzt::kSeg) void lz4_train_apply_kernel(tyche_batch_
     }
 }
 
-size_t blocks_per_cu(const void *kernel, size_t lds) {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, (int)kThreadsT, lds) == hipSuccess && n > 0) return (size_t)n;
-    return 1;
-}
-
 }  // namespace
 
 hipError_t train_lz4_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t dict_len, hipStream_t s, uint8_t *dict_out,
@@ -186,9 +180,8 @@ hipError_t train_lz4_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t dict
     if ((e = hipMemsetAsync(base, 0, ub_off, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(ub, 0xFF, (size_t)count * sizeof(uint32_t), s)) != hipSuccess) return e;
 
-    const size_t ncu = prepare_launch((const void *)lz4_train_count_kernel);
     const size_t lds_count = sizeof(Ctl) + kBitmapBytesT + stage_bytes(in_cap);
-    const size_t grid_count = std::min<size_t>(count, ncu * blocks_per_cu((const void *)lz4_train_count_kernel, lds_count));
+    const size_t grid_count = page_grid((const void *)lz4_train_count_kernel, kThreadsT, lds_count, count);
     res->step = "count pass";
     hipLaunchKernelGGL(lz4_train_count_kernel, dim3((unsigned)grid_count), dim3(kThreadsT), lds_count, s, b, in_cap, table, st);
     if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -199,9 +192,8 @@ hipError_t train_lz4_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t dict
     res->too_long = h.too_long != 0;
     if (res->too_long || h.total_bytes > TYCHE_LZ4_TRAIN_MAX_BYTES) return hipSuccess;   // the caller names the rule
 
-    (void)prepare_launch((const void *)lz4_train_score_kernel);
     const size_t lds_score = sizeof(Ctl) + stage_bytes(in_cap) + ((size_t)in_cap / lzt::kStep + 1u) * sizeof(lzt::Blk);   // key_blocks(in_cap) entries
-    const size_t grid_score = std::min<size_t>(count, ncu * blocks_per_cu((const void *)lz4_train_score_kernel, lds_score));
+    const size_t grid_score = page_grid((const void *)lz4_train_score_kernel, kThreadsT, lds_score, count);
     res->step = "rounds";
     for (uint32_t r = 0; r < rounds; r++) {
         hipLaunchKernelGGL(lz4_train_score_kernel, dim3((unsigned)grid_score), dim3(kThreadsT), lds_score, s, b, in_cap, table,

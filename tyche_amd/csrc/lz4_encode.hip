@@ -541,18 +541,10 @@ __global__ __launch_bounds__(128, 3) void lz4_encode_split_kernel(tyche_batch_t 
         __syncthreads();
         const size_t next = (size_t)rfl(hdr->next_lo) | ((size_t)rfl(hdr->next_hi) << 32);
         PageRef pn;
-        u32x4 pf[kSplitPrefetch];
-        uint32_t nhead = 0, nvec = 0;
+        TYCHE_NEXT_PAGE(kSplitPrefetch);
         if (next < b.count) {
             pn = batch_page(b, next);
-            if (pn.src_len <= in_cap && pn.src_len > 0) {
-                const uintptr_t a = (uintptr_t)pn.src;
-                nhead = (uint32_t)(a & 15u);
-                nvec = (nhead + pn.src_len + 15u) >> 4;
-                const u32x4 *g = (const u32x4 *)(a - nhead);
-#pragma unroll
-                for (uint32_t k = 0; k < kSplitPrefetch; k++) pf[k] = gload_nt(g + min(tid + k * 2 * kWave, nvec - 1u));
-            }
+            TYCHE_NEXT_PAGE_FETCH(kSplitPrefetch, 2 * kWave, pn.src, pn.src_len, in_cap, tid)
         }
         const uint8_t *in = stage + head;
         const uint32_t L = p.src_len;
@@ -646,16 +638,7 @@ __global__ __launch_bounds__(128, 3) void lz4_encode_split_kernel(tyche_batch_t 
         page = next;
         p = pn;
         head = nhead;
-        if (p.src_len <= in_cap && p.src_len > 0) {
-            u32x4 *l = (u32x4 *)stage;
-#pragma unroll
-            for (uint32_t k = 0; k < kSplitPrefetch; k++) {
-                const uint32_t v = tid + k * 2 * kWave;
-                if (v < nvec) l[v] = pf[k];
-            }
-            const u32x4 *g = (const u32x4 *)((uintptr_t)p.src - nhead);
-            for (uint32_t v = tid + kSplitPrefetch * 2 * kWave; v < nvec; v += 2 * kWave) l[v] = gload_nt(g + v);
-        }
+        TYCHE_NEXT_PAGE_INSTALL(kSplitPrefetch, 2 * kWave, p.src, p.src_len, in_cap, stage, tid)
         if (tid == 0) {
             hdr->next_lo = hdr->next2_lo;
             hdr->next_hi = hdr->next2_hi;
@@ -707,7 +690,7 @@ __host__ __device__ constexpr uint32_t part_scratch(uint32_t in_cap) {   // a pa
 template <uint32_t kNW>
 constexpr uint32_t split_prefetch() { return (16384u / 16u + kNW * kWave - 1u) / (kNW * kWave); }   // 16 KiB per page
 
-template <uint32_t kNW>
+template <uint32_t kNW, bool kRagged>
 #ifndef TYCHE_ENC_WPE
 #define TYCHE_ENC_WPE 5   // amdgpu_waves_per_eu register budget of the split kernels (4 waves: 87 VGPRs, no spills; 0: none)
 #endif
@@ -750,18 +733,10 @@ __global__ __launch_bounds__(kNW * 64) TYCHE_ENC_WPE_ATTR void lz4_encode_splitn
         __syncthreads();
         const size_t next = (size_t)rfl(hdr->next_lo) | ((size_t)rfl(hdr->next_hi) << 32);
         PageRef pn;
-        u32x4 pf[kPf];
-        uint32_t nhead = 0, nvec = 0;
+        TYCHE_NEXT_PAGE(kPf);
         if (next < b.count) {
             pn = batch_page(b, next);
-            if (pn.src_len <= in_cap && pn.src_len > 0) {
-                const uintptr_t a = (uintptr_t)pn.src;
-                nhead = (uint32_t)(a & 15u);
-                nvec = (nhead + pn.src_len + 15u) >> 4;
-                const u32x4 *g = (const u32x4 *)(a - nhead);
-#pragma unroll
-                for (uint32_t k = 0; k < kPf; k++) pf[k] = gload_nt(g + min(tid + k * kT, nvec - 1u));
-            }
+            TYCHE_NEXT_PAGE_FETCH(kPf, kT, pn.src, pn.src_len, in_cap, tid)
         }
         const uint8_t *in = stage + head;
         const uint32_t L = p.src_len;
@@ -828,6 +803,15 @@ __global__ __launch_bounds__(kNW * 64) TYCHE_ENC_WPE_ATTR void lz4_encode_splitn
                     hdr->cursor[wave] = cur;
                 }
             }
+        } else if (kRagged && tid == 0) {
+            // a page above in_cap is not parsed, but its turn still claims: a stale next2 would send the
+            // workgroup over the page it claimed before once more -- for ever, if that one is too long as well.
+            // (kRagged: the batch has per-page lengths; with one length for all, none is above in_cap, and the
+            // kernel is the one without this branch -- with it the same parse runs 0.7-1.5 % slower, wherever
+            // the claim is put: profiles/README.md)
+            const size_t nx = (size_t)atomicAdd(ctr, 1u) + gridDim.x;
+            hdr->next2_lo = (uint32_t)nx;
+            hdr->next2_hi = (uint32_t)(nx >> 32);
         }
         __syncthreads();   // every part parsed
         if (wave == 0) {
@@ -878,16 +862,7 @@ __global__ __launch_bounds__(kNW * 64) TYCHE_ENC_WPE_ATTR void lz4_encode_splitn
         page = next;
         p = pn;
         head = nhead;
-        if (p.src_len <= in_cap && p.src_len > 0) {
-            u32x4 *l = (u32x4 *)stage;
-#pragma unroll
-            for (uint32_t k = 0; k < kPf; k++) {
-                const uint32_t v = tid + k * kT;
-                if (v < nvec) l[v] = pf[k];
-            }
-            const u32x4 *g = (const u32x4 *)((uintptr_t)p.src - nhead);
-            for (uint32_t v = tid + kPf * kT; v < nvec; v += kT) l[v] = gload_nt(g + v);
-        }
+        TYCHE_NEXT_PAGE_INSTALL(kPf, kT, p.src, p.src_len, in_cap, stage, tid)
         if (tid == 0) {
             hdr->next_lo = hdr->next2_lo;
             hdr->next_hi = hdr->next2_hi;
@@ -912,21 +887,10 @@ __global__ __launch_bounds__(64) void lz4_encode_kernel(tyche_batch_t b, uint32_
     for (;;) {
         const size_t next = ctr ? claim_page(ctr, lane) : page + stride;   // dynamic assignment (engine.h)
         PageRef pn;
-        u32x4 pf[kPrefetchVec];
-        uint32_t nhead = 0, nvec = 0;
+        TYCHE_NEXT_PAGE(kPrefetchVec);
         if (next < b.count) {
             pn = batch_page(b, next);
-            if (pn.src_len <= in_cap && pn.src_len > 0) {
-                uintptr_t a = (uintptr_t)pn.src;
-                nhead = (uint32_t)(a & 15u);
-                nvec = (nhead + pn.src_len + 15u) >> 4;
-                const u32x4 *g = (const u32x4 *)(a - nhead);
-#pragma unroll
-                for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                    const uint32_t v = lane + k * kWave;
-                    pf[k] = gload_nt(g + min(v, nvec - 1u));   // clamped: no branch, always in bounds
-                }
-            }
+            TYCHE_NEXT_PAGE_FETCH(kPrefetchVec, kWave, pn.src, pn.src_len, in_cap, lane)
         }
         int32_t rv;
         if (p.src_len > in_cap) {
@@ -945,16 +909,7 @@ __global__ __launch_bounds__(64) void lz4_encode_kernel(tyche_batch_t b, uint32_
         page = next;
         p = pn;
         head = nhead;
-        if (p.src_len <= in_cap && p.src_len > 0) {
-            u32x4 *l = (u32x4 *)stage;
-#pragma unroll
-            for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                const uint32_t v = lane + k * kWave;
-                if (v < nvec) l[v] = pf[k];
-            }
-            const u32x4 *g = (const u32x4 *)((uintptr_t)p.src - nhead);
-            for (uint32_t v = lane + kPrefetchVec * kWave; v < nvec; v += kWave) l[v] = gload_nt(g + v);
-        }
+        TYCHE_NEXT_PAGE_INSTALL(kPrefetchVec, kWave, p.src, p.src_len, in_cap, stage, lane)
     }
 }
 
@@ -997,18 +952,14 @@ hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_
     const uint32_t split_min = (uint32_t)std::max(0L, knob("LZ4_SPLIT_MIN", nw == 3 || nw == 4 || nw == 8 ? 8192L
                                                                                                        : (long)kSplitMin));
     if (!one_wave && in_cap >= split_min && (nw == 3 || nw == 4 || nw == 8)) {
-        const void *k = nw == 8   ? (const void *)lz4_encode_splitn_kernel<8>
-                        : nw == 4 ? (const void *)lz4_encode_splitn_kernel<4>
-                                  : (const void *)lz4_encode_splitn_kernel<3>;
+        const bool rg = b.src_lengths != nullptr;   // (kRagged: only such a batch can hold a page above in_cap)
+        const void *k = nw == 8   ? (rg ? (const void *)lz4_encode_splitn_kernel<8, true> : (const void *)lz4_encode_splitn_kernel<8, false>)
+                        : nw == 4 ? (rg ? (const void *)lz4_encode_splitn_kernel<4, true> : (const void *)lz4_encode_splitn_kernel<4, false>)
+                                  : (rg ? (const void *)lz4_encode_splitn_kernel<3, true> : (const void *)lz4_encode_splitn_kernel<3, false>);
         const uint32_t T = (uint32_t)nw * kWave;
         const size_t lds = (nw == 8 ? split_stage_off<8>() : nw == 4 ? split_stage_off<4>() : split_stage_off<3>()) +
                            ((in_cap + 16u + kPad + 15u) & ~15u);
-        const size_t ncu = prepare_launch(k);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, (int)T, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        const long cap_cu = knob("LZ4_ENC_PAGES_PER_CU", 0);   // (occupancy A/B: resident pages per CU)
-        if (cap_cu > 0) per_cu = std::min<int>(per_cu, (int)cap_cu);
-        const size_t grid = std::min<size_t>(b.count, ncu * (size_t)per_cu);
+        const size_t grid = page_grid(k, T, lds, b.count, "LZ4_ENC_PAGES_PER_CU");
         const uint32_t pws = nw == 8 ? part_scratch<8>(in_cap) : nw == 4 ? part_scratch<4>(in_cap) : part_scratch<3>(in_cap);
         uint32_t seed = (uint32_t)std::max(0L, knob("LZ4_ENC_SEED", nw == 3 ? 10240L : nw == 4 ? 8192L : (long)kSeed)) &
                         ~(kWave - 1u);   // positions seeded before a part
@@ -1032,12 +983,7 @@ hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_
     }
     if (!one_wave && in_cap >= split_min) {
         const size_t lds = kSplitStage + ((in_cap + 16u + kPad + 15u) & ~15u);
-        const size_t ncu = prepare_launch((const void *)lz4_encode_split_kernel);
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lz4_encode_split_kernel, 2 * kWave,
-                                                         lds) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        const size_t grid = std::min<size_t>(b.count, ncu * (size_t)per_cu);
+        const size_t grid = page_grid((const void *)lz4_encode_split_kernel, 2 * kWave, lds, b.count);
         // B's scratch: its half's worst case (LZ4_compressBound of L - H < in_cap / 2 + 64), 256-byte aligned
         const uint32_t ws_stride = (lz4_bound(in_cap / 2u + kWave) + 64u + 255u) & ~255u;
         ScratchLease ws(s, grid * (size_t)ws_stride);
@@ -1051,9 +997,7 @@ hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_
     }
     const size_t lds = kHashSize * sizeof(uint16_t) + 4 * kWave + kWave * 8 + kOutRing +
                        ((in_cap + 16u + kPad + 15u) & ~15u);
-    const size_t ncu = prepare_launch((const void *)lz4_encode_kernel);
-    const size_t per_cu = waves_per_cu((const void *)lz4_encode_kernel, lds);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)lz4_encode_kernel, kWave, lds, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(lz4_encode_kernel, dim3((unsigned)grid), dim3(kWave), lds, s, b, in_cap, ctr.get());

@@ -123,9 +123,7 @@ hipError_t launch_lz4_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const
     if (b.count == 0) return hipSuccess;
     if ((uint64_t)in_cap + d.dlen > lzd::kWindowMax || d.enc_len > d.dlen || (d.enc_len & 63u)) return hipErrorInvalidValue;
     const size_t lds = kFrontD + d.enc_len + page_vec_bytes(in_cap);
-    const size_t ncu = prepare_launch((const void *)lz4_encode_dict_kernel);
-    const size_t per_cu = waves_per_cu((const void *)lz4_encode_dict_kernel, lds);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)lz4_encode_dict_kernel, kWave, lds, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(lz4_encode_dict_kernel, dim3((unsigned)grid), dim3(kWave), lds, s, b, in_cap, d,

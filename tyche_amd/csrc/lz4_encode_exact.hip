@@ -12,7 +12,7 @@
 // reference do.
 //
 // One 64-lane wave per page, looping over pages with the next page prefetched
-// into registers (as lz4_encode_kernel).  The page is staged in LDS next to the
+// into registers (TYCHE_NEXT_PAGE, lds_io.h).  The page is staged in LDS next to the
 // reference's table: 8192 16-bit positions (16 KiB), zeroed per page.  The
 // encoder reads no byte past the page, so the stage is the 16-byte vectors that
 // hold it: 32 KiB per wave at 16 KiB pages (4 pages per CU by LDS, one wave per
@@ -50,21 +50,10 @@ __global__ __launch_bounds__(64) void lz4_encode_exact_kernel(tyche_batch_t b, u
     for (;;) {
         const size_t next = claim_page(ctr, lane);   // dynamic assignment (engine.h)
         PageRef pn;
-        u32x4 pf[kPrefetchVecX];
-        uint32_t nhead = 0, nvec = 0;
+        TYCHE_NEXT_PAGE(kPrefetchVecX);
         if (next < b.count) {
             pn = batch_page(b, next);
-            if (pn.src_len <= in_cap && pn.src_len > 0) {
-                uintptr_t a = (uintptr_t)pn.src;
-                nhead = (uint32_t)(a & 15u);
-                nvec = (nhead + pn.src_len + 15u) >> 4;
-                const u32x4 *g = (const u32x4 *)(a - nhead);
-#pragma unroll
-                for (uint32_t k = 0; k < kPrefetchVecX; k++) {
-                    const uint32_t v = lane + k * kWaveX;
-                    pf[k] = gload_nt(g + min(v, nvec - 1u));   // clamped: no branch, always in bounds
-                }
-            }
+            TYCHE_NEXT_PAGE_FETCH(kPrefetchVecX, kWaveX, pn.src, pn.src_len, in_cap, lane)
         }
         int32_t rv;
         if (p.src_len > in_cap) {
@@ -82,16 +71,7 @@ __global__ __launch_bounds__(64) void lz4_encode_exact_kernel(tyche_batch_t b, u
         page = next;
         p = pn;
         head = nhead;
-        if (p.src_len <= in_cap && p.src_len > 0) {
-            u32x4 *l = (u32x4 *)stage;
-#pragma unroll
-            for (uint32_t k = 0; k < kPrefetchVecX; k++) {
-                const uint32_t v = lane + k * kWaveX;
-                if (v < nvec) l[v] = pf[k];
-            }
-            const u32x4 *g = (const u32x4 *)((uintptr_t)p.src - nhead);
-            for (uint32_t v = lane + kPrefetchVecX * kWaveX; v < nvec; v += kWaveX) l[v] = gload_nt(g + v);
-        }
+        TYCHE_NEXT_PAGE_INSTALL(kPrefetchVecX, kWaveX, p.src, p.src_len, in_cap, stage, lane)
     }
 }
 
@@ -100,11 +80,7 @@ __global__ __launch_bounds__(64) void lz4_encode_exact_kernel(tyche_batch_t b, u
 hipError_t launch_lz4_encode_exact(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
     // table | the 16-byte vectors that hold a page (stage_in: a page may start at any byte of its first vector)
     const size_t lds = kTableBytes + ((in_cap + 15u + 15u) & ~15u);
-    const size_t ncu = prepare_launch((const void *)lz4_encode_exact_kernel);
-    size_t per_cu = waves_per_cu((const void *)lz4_encode_exact_kernel, lds);
-    const long cap_cu = knob("LZ4_EXACT_PAGES_PER_CU", 0);   // (occupancy A/B: resident pages per CU; 0: what fits)
-    if (cap_cu > 0) per_cu = std::min<size_t>(per_cu, (size_t)cap_cu);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)lz4_encode_exact_kernel, kWaveX, lds, b.count, "LZ4_EXACT_PAGES_PER_CU");
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(lz4_encode_exact_kernel, dim3((unsigned)grid), dim3(kWaveX), lds, s, b, in_cap, ctr.get());

@@ -60,9 +60,7 @@ __global__ __launch_bounds__(64) void lz4_encode_large_kernel(tyche_batch_t b, u
 hipError_t launch_lz4_encode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t min_len, hipStream_t s) {
     if (b.count == 0) return hipSuccess;
     if (in_cap > TYCHE_LZ4_MAX_PAGE) return hipErrorInvalidValue;
-    const size_t ncu = prepare_launch((const void *)lz4_encode_large_kernel);
-    const size_t per_cu = waves_per_cu((const void *)lz4_encode_large_kernel, kEncLargeLds);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)lz4_encode_large_kernel, 64, kEncLargeLds, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(lz4_encode_large_kernel, dim3((unsigned)grid), dim3(64), kEncLargeLds, s, b, in_cap, min_len,

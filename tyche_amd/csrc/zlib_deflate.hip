@@ -596,21 +596,10 @@ __global__ __launch_bounds__(64) void zlib_deflate_kernel(tyche_batch_t b, uint3
     for (;;) {
         const size_t next = ctr ? claim_page(ctr, lane) : page + stride;   // dynamic assignment (engine.h)
         PageRef pn;
-        u32x4 pf[kPrefetchVec];
-        uint32_t nhead = 0, nvec = 0;
+        TYCHE_NEXT_PAGE(kPrefetchVec);
         if (next < b.count) {
             pn = batch_page(b, next);
-            if (pn.src_len <= in_cap && pn.src_len > 0) {
-                uintptr_t a = (uintptr_t)pn.src;
-                nhead = (uint32_t)(a & 15u);
-                nvec = (nhead + pn.src_len + 15u) >> 4;
-                const u32x4 *g = (const u32x4 *)(a - nhead);
-#pragma unroll
-                for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                    const uint32_t v = lane + k * kWave;
-                    pf[k] = gload_nt(g + min(v, nvec - 1u));   // clamped: no branch, always in bounds
-                }
-            }
+            TYCHE_NEXT_PAGE_FETCH(kPrefetchVec, kWave, pn.src, pn.src_len, in_cap, lane)
         }
         int32_t rv;
         if (p.src_len > in_cap) {
@@ -628,16 +617,7 @@ __global__ __launch_bounds__(64) void zlib_deflate_kernel(tyche_batch_t b, uint3
         page = next;
         p = pn;
         head = nhead;
-        if (p.src_len <= in_cap && p.src_len > 0) {
-            u32x4 *l = (u32x4 *)stage;
-#pragma unroll
-            for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                const uint32_t v = lane + k * kWave;
-                if (v < nvec) l[v] = pf[k];
-            }
-            const u32x4 *g = (const u32x4 *)((uintptr_t)p.src - nhead);
-            for (uint32_t v = lane + kPrefetchVec * kWave; v < nvec; v += kWave) l[v] = gload_nt(g + v);
-        }
+        TYCHE_NEXT_PAGE_INSTALL(kPrefetchVec, kWave, p.src, p.src_len, in_cap, stage, lane)
     }
 }
 
@@ -648,9 +628,7 @@ hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStrea
     if (in_cap > 65535u) return hipErrorInvalidValue;    // 16-bit positions in the parse
     const size_t lds = kTableSlots * sizeof(uint16_t) + kStageWords * 4 + kWave + kWave * 8 +
                        ((in_cap + 16u + kPad + 15u) & ~15u);
-    const size_t ncu = prepare_launch((const void *)zlib_deflate_kernel);
-    const size_t per_cu = waves_per_cu((const void *)zlib_deflate_kernel, lds);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)zlib_deflate_kernel, kWave, lds, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     // per-wave record scratch: L / 3 + 2 records of 8 bytes (each record but the

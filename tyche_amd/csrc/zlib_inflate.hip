@@ -1307,11 +1307,7 @@ hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStre
             const void *k = wide ? k512 : k256;
             const uint32_t threads = wide ? 512u : 256u;
             if (wide) (void)prepare_launch(k512);
-            int per_cu = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, (int)threads, lds + 128u) != hipSuccess ||
-                per_cu < 1)
-                per_cu = 1;
-            const size_t grid = std::min<size_t>(b.count, ncu * (size_t)per_cu);
+            const size_t grid = wide ? b.count : std::min<size_t>(b.count, ncu * blocks_per_cu(k, threads, lds + 128u));
             WorkCounter ctr(s, grid < b.count);
             if (grid < b.count && !ctr.get()) return hipErrorOutOfMemory;
             unsigned *cp = grid < b.count ? ctr.get() : nullptr;
@@ -1322,9 +1318,7 @@ hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStre
             return hipGetLastError();
         }
         if (lds <= 160 * 1024) {
-            const size_t ncu = prepare_launch((const void *)zlib_inflate_par_kernel);
-            const size_t per_cu = waves_per_cu((const void *)zlib_inflate_par_kernel, lds);
-            const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+            const size_t grid = page_grid((const void *)zlib_inflate_par_kernel, kWave, lds, b.count);
             WorkCounter ctr(s, grid < b.count);
             if (!ctr.get()) return hipErrorOutOfMemory;
             hipLaunchKernelGGL(zlib_inflate_par_kernel, dim3((unsigned)grid), dim3(kWave), lds, s, b, out_cap,
@@ -1334,9 +1328,7 @@ hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStre
     }
     const size_t lds = off_lens + 320 + 2 * 320 + 2 * 32;
     if (lds > 160 * 1024) return hipErrorInvalidValue;
-    const size_t ncu = prepare_launch((const void *)zlib_inflate_kernel);
-    const size_t per_cu = waves_per_cu((const void *)zlib_inflate_kernel, lds);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)zlib_inflate_kernel, kWave, lds, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(zlib_inflate_kernel, dim3((unsigned)grid), dim3(kWave), lds, s, b, out_cap, off_lens,

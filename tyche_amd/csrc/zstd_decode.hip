@@ -2569,9 +2569,7 @@ extern "C" int tyche_debug_zstd_decode_profile(unsigned long long *host16, int r
 static hipError_t launch_fused(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s) {
     const Layout lay = make_layout(in_cap, out_cap);
     if (lay.total > 160u * 1024u) return hipErrorInvalidValue;
-    const size_t ncu = prepare_launch((const void *)zstd_decode_kernel);
-    const size_t per_cu = waves_per_cu((const void *)zstd_decode_kernel, lay.total);
-    const size_t grid = std::min<size_t>(b.count, ncu * per_cu);
+    const size_t grid = page_grid((const void *)zstd_decode_kernel, kWave, lay.total, b.count);
     WorkCounter ctr(s, grid < b.count);
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(zstd_decode_kernel, dim3((unsigned)grid), dim3(kWave), lay.total, s, b, (size_t)0, b.count, in_cap,
@@ -2643,9 +2641,9 @@ hipError_t launch_zstd_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t 
     // (~70 KiB at 32 KiB pages, above the 64 KiB default): its limit must be raised here too, and
     // before cuf is sized, whether or not launch_fused ran earlier in this process
     if (seqexec) (void)prepare_launch((const void *)zstd_decode_kernel);
-    const size_t cu1 = waves_per_cu((const void *)zstd_entropy_kernel, l1.total);
-    const size_t cu2 = lane_exec ? waves_per_cu(kx, lds_lane) : waves_per_cu((const void *)zstd_exec_kernel, lds2);
-    const size_t cuf = seqexec ? waves_per_cu((const void *)zstd_decode_kernel, lf.total) : 0;
+    const size_t cu1 = blocks_per_cu((const void *)zstd_entropy_kernel, 64, l1.total);
+    const size_t cu2 = lane_exec ? blocks_per_cu(kx, 64, lds_lane) : blocks_per_cu((const void *)zstd_exec_kernel, 64, lds2);
+    const size_t cuf = seqexec ? blocks_per_cu((const void *)zstd_decode_kernel, 64, lf.total) : 0;
     for (size_t first = 0; first < b.count; first += chunk) {
         const size_t n = std::min(chunk, b.count - first);
         const size_t g1 = std::min<size_t>(n, ncu * cu1);

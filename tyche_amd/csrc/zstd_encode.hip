@@ -1057,21 +1057,10 @@ __global__ __launch_bounds__(64) void zstd_encode_kernel(tyche_batch_t b, size_t
     for (;;) {
         const size_t next = ctr ? claim_page(ctr, lane) : page + stride;   // dynamic assignment (engine.h)
         PageRef pn;
-        u32x4 pf[kPrefetchVec];
-        uint32_t nhead = 0, nvec = 0;
+        TYCHE_NEXT_PAGE(kPrefetchVec);
         if (next < count) {
             pn = batch_page(b, first + next);
-            if (pn.src_len <= in_cap && pn.src_len > 0) {
-                uintptr_t a = (uintptr_t)pn.src;
-                nhead = (uint32_t)(a & 15u);
-                nvec = (nhead + pn.src_len + 15u) >> 4;
-                const u32x4 *g = (const u32x4 *)(a - nhead);
-#pragma unroll
-                for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                    const uint32_t v = lane + k * kWave;
-                    pf[k] = gload_nt(g + min(v, nvec - 1u));   // clamped: no branch, always in bounds
-                }
-            }
+            TYCHE_NEXT_PAGE_FETCH(kPrefetchVec, kWave, pn.src, pn.src_len, in_cap, lane)
         }
         int32_t rv;
         if (p.src_len > in_cap) {
@@ -1094,16 +1083,7 @@ __global__ __launch_bounds__(64) void zstd_encode_kernel(tyche_batch_t b, size_t
         page = next;
         p = pn;
         head = nhead;
-        if (p.src_len <= in_cap && p.src_len > 0) {
-            u32x4 *l = (u32x4 *)stage;
-#pragma unroll
-            for (uint32_t k = 0; k < kPrefetchVec; k++) {
-                const uint32_t v = lane + k * kWave;
-                if (v < nvec) l[v] = pf[k];
-            }
-            const u32x4 *g = (const u32x4 *)((uintptr_t)p.src - nhead);
-            for (uint32_t v = lane + kPrefetchVec * kWave; v < nvec; v += kWave) l[v] = gload_nt(g + v);
-        }
+        TYCHE_NEXT_PAGE_INSTALL(kPrefetchVec, kWave, p.src, p.src_len, in_cap, stage, lane)
     }
 }
 
@@ -1335,6 +1315,12 @@ __global__ __launch_bounds__(kNW * 64) void zstd_parse_split_kernel(tyche_batch_
                     hdr->next2_hi = (uint32_t)(nx >> 32);
                 }
             }
+        } else if (tid == 0) {
+            // a page above in_cap is not parsed, but its turn still claims: a stale next2 would send the
+            // workgroup over the page it claimed before once more -- for ever, if that one is too long as well
+            const size_t nx = (size_t)atomicAdd(ctr, 1u) + gridDim.x;
+            hdr->next2_lo = (uint32_t)nx;
+            hdr->next2_hi = (uint32_t)(nx >> 32);
         }
         __syncthreads();   // every part parsed
         bool ok = fits;
@@ -1765,8 +1751,7 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
     ScratchLease lease(s, split ? st_bytes + chunk * page_bytes : 0);
     if (!split || !lease.get()) {
         const void *k = (const void *)zstd_encode_kernel<false>;
-        const size_t ncu = prepare_launch(k);
-        const size_t grid = std::min<size_t>(b.count, ncu * waves_per_cu(k, lds));
+        const size_t grid = page_grid(k, kWave, lds, b.count);
         WorkCounter ctr(s, grid < b.count);
         if (!ctr.get()) return hipErrorOutOfMemory;
         hipLaunchKernelGGL(zstd_encode_kernel<false>, dim3((unsigned)grid), dim3(kWave), lds, s, b, (size_t)0, b.count,
@@ -1784,7 +1769,7 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
     (void)prepare_launch((const void *)zstd_block_kernel);
     (void)prepare_launch((const void *)zstd_fse_kernel);
     (void)prepare_launch((const void *)zstd_pack_kernel);
-    const size_t cu1 = waves_per_cu(k1, lds1), cu2 = waves_per_cu((const void *)zstd_block_kernel, kA2Lds);
+    const size_t cu1 = blocks_per_cu(k1, 64, lds1), cu2 = blocks_per_cu((const void *)zstd_block_kernel, 64, kA2Lds);
     // pass A1 on 1 to 4 waves per page (1: the one-wave parse, 4-way buckets, up to 16 KiB):
     // 4 by default above 16 KiB.  Round 3, 32 KiB bench pages with one block per page
     // (profiles/r03_zstd_parse_ab.log): 2 parts 793 ms per 1M pages at ratio 4.940; 3 parts 823
@@ -1798,9 +1783,7 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
     size_t cup = 1;
     if (psplit) {
         (void)prepare_launch(kp);
-        int per = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kp, (int)(pw * kWave), ldsp) == hipSuccess && per > 0)
-            cup = (size_t)per;
+        cup = blocks_per_cu(kp, (uint32_t)pw * kWave, ldsp);
     }
     // pass A1 on two pipelined waves (TYCHE_ZSTD_PARSE_PIPE=1; default 0: one wave per page)
     const bool pipe = !psplit && knob("ZSTD_PARSE_PIPE", 0) != 0;
@@ -1808,10 +1791,7 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
     size_t cuq = 1;
     if (pipe) {
         (void)prepare_launch((const void *)zstd_parse_pipe_kernel);
-        int per = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)zstd_parse_pipe_kernel, 2 * (int)kWave, ldsq) ==
-                hipSuccess && per > 0)
-            cuq = (size_t)per;
+        cuq = blocks_per_cu((const void *)zstd_parse_pipe_kernel, 2 * kWave, ldsq);
     }
     for (size_t first = 0; first < b.count; first += chunk) {
         const size_t n = std::min(chunk, b.count - first);
