@@ -196,6 +196,76 @@ int tyche_decompress_batch(int compressor_id, const tyche_batch_t *batch, void *
  * compressBound (zlib compress.c:74-78) or ZSTD_compressBound (zstd_compress.c:37) */
 uint32_t tyche_compress_bound(int compressor_id, uint32_t n);
 
+/* ---- packed store: compressed pages at their compressed size --------------- */
+/* tyche_compress_batch leaves page i's stream in a slot of tyche_compress_bound
+ * bytes.  tyche_pack_batch appends the streams of one such batch to an arena, one
+ * after another, and returns where each went; every decoder reads them there
+ * through src_offsets / src_lengths (tyche_batch_t), at any alignment.
+ *
+ * The rule (pack_core.h; tyche_pack_plan is the same code on host arrays):
+ *   len_i = results[i] if 0 < results[i] and (max_length == 0 or results[i] <=
+ *           max_length), else 0 -- 0, INT32_MIN and every negative result mean
+ *           "no stream", and so does a result above a declared max_length;
+ *   o_0 = round_up(state[1], align), o_{i+1} = round_up(o_i + len_i, align): a
+ *           zero-length page takes no room;
+ *   offsets[i] = o_i and lengths[i] = len_i are always written;
+ *   end = o_{n-1} + len_{n-1}, not rounded; for count == 0, end = state[1] and
+ *           nothing is read or written;
+ *   the batch is stored iff no earlier append into this state was refused
+ *           (state[0] == state[1] on entry) and end <= arena_capacity;
+ *   stored:  every stream is copied to arena + o_i, state[0] = state[1] = end;
+ *   refused: no arena byte is written, state[0] stays, state[1] = end.
+ * Refusal is sticky: after one refused append every later one is refused too, so
+ * an arena never has holes, and state[1] says how large an arena would have held
+ * everything.  The invariant a caller relies on: page i is in the arena iff
+ * offsets[i] + lengths[i] <= state[0] after the call.  A fresh store has state
+ * {0, 0}.  The decision is made on the device: appends chain on a stream with no
+ * host round trip, and the call never synchronises.
+ *
+ * Contract, beside the batch contract above: nothing outside [arena + o_i, arena
+ * + o_i + len_i) is written -- not the alignment gaps, not the bytes before o_0,
+ * not the bytes at or past end; src is never written; no arena byte depends on a
+ * source byte outside [src_i, src_i + len_i) (the slots' tails hold codec
+ * scratch), although whole 16-byte lines around a stream may be read; src_i,
+ * arena and state[1] may have any byte alignment; arena must not overlap src.
+ * Page i's stream is at src + src_offsets[i], or src + i * src_stride when
+ * src_offsets is NULL.
+ *
+ * Refused with TYCHE_E_BAD_ARGS, the rule and the number in tyche_last_error(),
+ * before any device call: align zero, not a power of two or above
+ * TYCHE_PACK_MAX_ALIGN; count > 0 with src, results, arena, state, offsets or
+ * lengths NULL; count above TYCHE_PACK_MAX_PAGES (2^28: page indices are 32-bit
+ * in the kernels, the five 64-probe rounds of the copy's search reach 2^30, and
+ * the one-workgroup scan of the tile sums takes count / 2^18 rounds).  No device
+ * or a failed launch is TYCHE_E_DEVICE.  tyche_pack_plan returns end, or
+ * UINT64_MAX for the same bad arguments (offsets and lengths may be NULL there).
+ *
+ * Compaction after evictions is the same call: src = the old arena, src_offsets
+ * = the surviving pages' offsets, results = their lengths (the same 32-bit
+ * values), arena = a second arena, a fresh state. */
+#define TYCHE_PACK_MAX_ALIGN 4096u
+#define TYCHE_PACK_MAX_PAGES (1u << 28)
+typedef struct tyche_pack {
+    size_t count;
+    /* where the streams are: the dst side of the compress batch that wrote them */
+    const void *src;
+    const uint64_t *src_offsets;
+    uint64_t src_stride;
+    const int32_t *results;   /* device: compress results; <= 0 (0, INT32_MIN, any negative) = no stream */
+    uint32_t max_length;      /* 0 = none; a result above it counts as no stream */
+    void *arena;
+    uint64_t arena_capacity;
+    uint32_t align;           /* power of two, 1..TYCHE_PACK_MAX_ALIGN */
+    uint64_t *state;          /* device, 2 words: state[0] = used, state[1] = wanted */
+    uint64_t *offsets;        /* device, count entries, out */
+    uint32_t *lengths;        /* device, count entries, out */
+} tyche_pack_t;
+/* asynchronous on `stream` (a hipStream_t, NULL = default stream), no host sync */
+int tyche_pack_batch(const tyche_pack_t *p, void *stream);
+/* the same rule on host arrays, no GPU: for tests and for callers that size an arena */
+uint64_t tyche_pack_plan(size_t n, const int32_t *results, uint32_t max_length, uint32_t align, uint64_t capacity,
+                         uint64_t state[2], uint64_t *offsets, uint32_t *lengths);
+
 /* ---- LZ4 with a shared dictionary ----------------------------------------- */
 /* The engine compresses every page on its own; a dictionary is a common prefix
  * that a page's matches may reach into (LZ4_loadDict + LZ4_compress_fast_continue

@@ -37,6 +37,8 @@ RESULT_TOO_LARGE = -(2 ** 31)
 LZ4_DICT_MAX = 32768    # TYCHE_LZ4_DICT_MAX
 LZ4_TRAIN_MAX_BYTES = 64 << 20   # TYCHE_LZ4_TRAIN_MAX_BYTES
 LZ4_TRAIN_MAX_PAGES = 1 << 19    # TYCHE_LZ4_TRAIN_MAX_PAGES
+PACK_MAX_ALIGN = 4096            # TYCHE_PACK_MAX_ALIGN
+PACK_MAX_PAGES = 1 << 28         # TYCHE_PACK_MAX_PAGES
 
 # buffer flags, src/buffer.h:23-33
 FLAG_COMPRESSING = 1 << 5
@@ -87,6 +89,25 @@ class Batch(ctypes.Structure):
     ]
 
 
+class Pack(ctypes.Structure):
+    """tyche_pack_t (include/tyche_codec.h)."""
+
+    _fields_ = [
+        ("count", ctypes.c_size_t),
+        ("src", ctypes.c_void_p),
+        ("src_offsets", ctypes.c_void_p),
+        ("src_stride", ctypes.c_uint64),
+        ("results", ctypes.c_void_p),
+        ("max_length", ctypes.c_uint32),
+        ("arena", ctypes.c_void_p),
+        ("arena_capacity", ctypes.c_uint64),
+        ("align", ctypes.c_uint32),
+        ("state", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("lengths", ctypes.c_void_p),
+    ]
+
+
 _BufP = ctypes.POINTER(Buffer)
 _vpp = ctypes.POINTER(ctypes.c_void_p)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -110,6 +131,9 @@ SIGNATURES = {
     "tyche_compress_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Batch), ctypes.c_void_p]),
     "tyche_decompress_batch": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(Batch), ctypes.c_void_p]),
     "tyche_compress_bound": (ctypes.c_uint32, [ctypes.c_int, ctypes.c_uint32]),
+    "tyche_pack_batch": (ctypes.c_int, [ctypes.POINTER(Pack), ctypes.c_void_p]),
+    "tyche_pack_plan": (ctypes.c_uint64, [ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "tyche_lz4_dict_create": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_uint32]),
     "tyche_lz4_dict_destroy": (None, [ctypes.c_void_p]),
     "tyche_lz4_dict_length": (ctypes.c_uint32, [ctypes.c_void_p]),

@@ -24,6 +24,12 @@ the default encoder's time, restored by ``decompress_pages`` as any other block
 as without the knob; ``LZ4_EXACT=1`` beside it raises ``DeviceError``
 (``TYCHE_E_BAD_ARGS``).
 
+Packed store: ``pack_pages`` appends the streams of ``compress_pages`` to a 1-D
+arena at their compressed size (``tyche_pack_batch``) and returns offsets and
+lengths, ``decompress_packed`` decodes from them, ``compress_pages_packed`` does
+compress + append a chunk of rows at a time.  A store's state is two int64 words
+on the device, ``{used, wanted}``; the device decides whether an append fits.
+
 Shared dictionary (LZ4 only): ``dictionary=Lz4Dict(bytes)`` makes the dictionary
 and each row one LZ4 window -- the blocks are what
 ``LZ4_decompress_safe_usingDict`` restores, and need the same dictionary to be
@@ -225,6 +231,106 @@ def compress_ragged(src: torch.Tensor, offsets: torch.Tensor, lengths: torch.Ten
                    dst_capacities=_ptr(capacities), results=_ptr(results))
     _compress_call(compressor_id, level, b, _stream_handle(src.device), dictionary)
     return out, results
+
+
+def new_pack_state(device) -> torch.Tensor:
+    """A fresh packed store's state: {used, wanted} = {0, 0} (two 64-bit words on the device)."""
+    return torch.zeros((2,), dtype=torch.int64, device=device)
+
+
+def _check_vec(t: torch.Tensor, name: str, dtype, n: int) -> None:
+    if not t.is_cuda or t.dtype != dtype or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous device tensor of {n} {dtype} values")
+
+
+def pack_pages(slots, comp_len: torch.Tensor, arena: torch.Tensor, state: torch.Tensor | None = None, align: int = 16,
+               offsets: torch.Tensor | None = None, lengths: torch.Tensor | None = None, max_length: int = 0):
+    """Appends the streams of a compress batch to ``arena`` at their compressed size
+    (tyche_pack_batch); returns (offsets, lengths, state).
+
+    ``slots`` is the (n, slot) tensor of ``compress_pages`` with ``comp_len`` its results; or, to
+    compact a store after evictions, ``(old_arena, offsets)`` with ``comp_len`` the surviving pages'
+    lengths.  ``arena`` is a 1-D uint8 device tensor that does not overlap the source.  ``state``
+    (two int64 words: used, wanted) is appended to; without one a fresh store is started.  Page i
+    went to ``arena[offsets[i] : offsets[i] + lengths[i]]`` iff ``offsets[i] + lengths[i] <= state[0]``
+    afterwards; an append that does not fit stores nothing, and every later one into that state is
+    refused too, with ``state[1]`` the arena size that would have held everything.  Offsets are int64,
+    lengths int32 (the bits of the C API's unsigned values).  Asynchronous on the current stream;
+    the decision is made on the device, so appends chain without a host sync.
+    """
+    if isinstance(slots, (tuple, list)):
+        src, src_offsets = slots
+        if not src.is_cuda or src.dtype != torch.uint8 or not src.is_contiguous():
+            raise ValueError("the source arena must be a contiguous uint8 device tensor")
+        n = src_offsets.numel()
+        _check_vec(src_offsets, "the source offsets", torch.int64, n)
+        stride = 0
+    else:
+        _check_pages(slots, "slots")
+        src, src_offsets, n, stride = slots, None, slots.shape[0], slots.shape[1]
+    if not arena.is_cuda or arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError("arena must be a contiguous 1-D uint8 device tensor")
+    _check_vec(comp_len, "comp_len", torch.int32, n)
+    if state is None:
+        state = new_pack_state(arena.device)
+    _check_vec(state, "state", torch.int64, 2)
+    if offsets is None:
+        offsets = torch.empty((n,), dtype=torch.int64, device=arena.device)
+    if lengths is None:
+        lengths = torch.empty((n,), dtype=torch.int32, device=arena.device)
+    _check_vec(offsets, "offsets", torch.int64, n)
+    _check_vec(lengths, "lengths", torch.int32, n)
+    p = _lib.Pack(count=n, src=_ptr(src), src_offsets=_ptr(src_offsets) if src_offsets is not None else None,
+                  src_stride=stride, results=_ptr(comp_len), max_length=max_length, arena=_ptr(arena),
+                  arena_capacity=arena.numel(), align=align, state=_ptr(state), offsets=_ptr(offsets), lengths=_ptr(lengths))
+    _lib.check(_lib.load().tyche_pack_batch(ctypes.byref(p), _stream_handle(arena.device)), "tyche_pack_batch")
+    return offsets, lengths, state
+
+
+def decompress_packed(arena: torch.Tensor, offsets: torch.Tensor, lengths: torch.Tensor, page_len: int,
+                      compressor_id: int = LZ4_COMPRESSOR_ID, out: torch.Tensor | None = None,
+                      rv: torch.Tensor | None = None, max_comp_len: int = 0, dictionary: Lz4Dict | None = None):
+    """Decompress page i from ``arena[offsets[i] : offsets[i] + lengths[i]]`` (what ``pack_pages``
+    returned) into a page_len row; returns (out, rv) as ``decompress_pages`` does.  One batch with
+    src_offsets / src_lengths; ``max_comp_len`` (optional) bounds the lengths for LDS sizing."""
+    n = offsets.numel()
+    _check_vec(offsets, "offsets", torch.int64, n)
+    _check_vec(lengths, "lengths", torch.int32, n)
+    if out is None:
+        out = torch.empty((n, page_len), dtype=torch.uint8, device=arena.device)
+    if rv is None:
+        rv = torch.empty((n,), dtype=torch.int32, device=arena.device)
+    _check_pages(out, "out")
+    b = _lib.Batch(count=n, src=_ptr(arena), src_offsets=_ptr(offsets), src_lengths=_ptr(lengths),
+                   max_src_length=max_comp_len, dst=_ptr(out), dst_stride=out.shape[1], dst_capacity=page_len,
+                   results=_ptr(rv))
+    _decompress_call(compressor_id, b, _stream_handle(arena.device), dictionary)
+    return out, rv
+
+
+def compress_pages_packed(pages: torch.Tensor, arena: torch.Tensor, state: torch.Tensor | None = None,
+                          chunk_pages: int = 65536, compressor_id: int = LZ4_COMPRESSOR_ID, level: int = 1,
+                          align: int = 16, dictionary: Lz4Dict | None = None):
+    """``compress_pages`` + ``pack_pages``, ``chunk_pages`` rows at a time through one reused slot
+    tensor: beside the arena, a million 16 KiB pages need one chunk's slots (about 1 GiB at the
+    default) instead of 17 GB.  Returns (offsets, lengths, state) for all rows, as one ``pack_pages``
+    over all of them would.  No host sync inside: every chunk's compress and append are enqueued on
+    the current stream, which orders the reuse of the slots."""
+    _check_pages(pages, "pages")
+    n, page_len = pages.shape
+    chunk = max(1, min(int(chunk_pages), max(n, 1)))
+    dev = pages.device
+    slots = torch.empty((chunk, slot_size(page_len, compressor_id)), dtype=torch.uint8, device=dev)
+    clen = torch.empty((chunk,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((n,), dtype=torch.int64, device=dev)
+    lengths = torch.empty((n,), dtype=torch.int32, device=dev)
+    if state is None:
+        state = new_pack_state(dev)
+    for a in range(0, n, chunk):
+        b = min(a + chunk, n)
+        compress_pages(pages[a:b], compressor_id, level, out=slots[:b - a], out_len=clen[:b - a], dictionary=dictionary)
+        pack_pages(slots[:b - a], clen[:b - a], arena, state, align, offsets[a:b], lengths[a:b])
+    return offsets, lengths, state
 
 
 def pagegen(n: int, page_len: int, seed: int = 20170303, first: int = 0, dist: int = 0,

@@ -127,6 +127,12 @@ struct TrainResult {
 };
 hipError_t train_lz4_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t dict_len, hipStream_t s, uint8_t *dict_out,
                           TrainResult *res);
+// The packed store (pack.hip; the rule is pack_core.h's): plan launches and the tiled copy of one
+// tyche_pack_batch call (arguments already checked, count > 0); *step names what was being done when
+// an error is returned.  pack_plan_host is the same rule over host arrays (tyche_pack_plan).
+hipError_t launch_pack(const tyche_pack_t &p, hipStream_t s, const char **step);
+uint64_t pack_plan_host(size_t n, const int32_t *results, uint32_t max_length, uint32_t align, uint64_t capacity,
+                        uint64_t state[2], uint64_t *offsets, uint32_t *lengths);
 hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);

@@ -1805,6 +1805,53 @@ int tyche_decompress_batch(int compressor_id, const tyche_batch_t *batch, void *
     return TYCHE_E_OK;
 }
 
+// --------------------------------------------------------------- packed store
+// the argument rules shared by tyche_pack_batch and tyche_pack_plan; 0 or TYCHE_E_BAD_ARGS with the reason
+static int pack_args(const char *what, size_t count, uint32_t align, bool missing) {
+    if (align == 0 || (align & (align - 1u)) != 0 || align > TYCHE_PACK_MAX_ALIGN) {
+        t_error = std::string(what) + ": align must be a power of two from 1 to TYCHE_PACK_MAX_ALIGN (" +
+                  std::to_string(TYCHE_PACK_MAX_ALIGN) + "), got " + std::to_string(align);
+        return TYCHE_E_BAD_ARGS;
+    }
+    if (count > TYCHE_PACK_MAX_PAGES) {
+        t_error = std::string(what) + ": count may be at most TYCHE_PACK_MAX_PAGES (" + std::to_string(TYCHE_PACK_MAX_PAGES) +
+                  "), got " + std::to_string(count);
+        return TYCHE_E_BAD_ARGS;
+    }
+    if (count > 0 && missing) {
+        t_error = std::string(what) + ": a batch of " + std::to_string(count) + " pages needs " +
+                  (strcmp(what, "tyche_pack_plan") == 0 ? "results and state" : "src, results, arena, state, offsets and lengths") +
+                  " (one is NULL)";
+        return TYCHE_E_BAD_ARGS;
+    }
+    return TYCHE_E_OK;
+}
+
+int tyche_pack_batch(const tyche_pack_t *p, void *stream) {
+    if (!p) {
+        t_error = "tyche_pack_batch: the tyche_pack_t is NULL";
+        return TYCHE_E_BAD_ARGS;
+    }
+    if (int rc = pack_args("tyche_pack_batch", p->count, p->align,
+                           !p->src || !p->results || !p->arena || !p->state || !p->offsets || !p->lengths))
+        return rc;
+    if (p->count == 0) return TYCHE_E_OK;
+    DeviceGuard keep;
+    if (keep.saved < 0) return fail_msg("no HIP device available (the codec runs only on the GPU)");
+    if (int rc = stream_device((hipStream_t)stream)) return rc;
+    const char *step = "";
+    hipError_t e = launch_pack(*p, (hipStream_t)stream, &step);
+    if (e != hipSuccess) return fail((std::string("pack (") + step + ")").c_str(), e);
+    return TYCHE_E_OK;
+}
+
+uint64_t tyche_pack_plan(size_t n, const int32_t *results, uint32_t max_length, uint32_t align, uint64_t capacity,
+                         uint64_t state[2], uint64_t *offsets, uint32_t *lengths) {
+    if (pack_args("tyche_pack_plan", n, align, !results || !state)) return UINT64_MAX;
+    if (n == 0) return state ? state[1] : 0u;
+    return pack_plan_host(n, results, max_length, align, capacity, state, offsets, lengths);
+}
+
 // ------------------------------------------------- shared LZ4 dictionary API
 tyche_lz4_dict_t *tyche_lz4_dict_create(const void *bytes, uint32_t len) { return dict_create(bytes, len); }
 
