@@ -2,6 +2,8 @@
 // gfx950 kernel files (the lz4_*, zlib_* and zstd_* .hip files, pagegen.hip):
 // their launchers, the batch's page metadata, and the launch plumbing they
 // share -- grid sizing, dynamic page assignment, scratch leases, knobs.
+// The host batch pipeline is a translation unit of its own, host_batch.hip (its
+// interface to engine.hip: host_batch.h; its chunk plan: host_chunk_core.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

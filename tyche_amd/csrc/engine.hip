@@ -6,7 +6,8 @@
 // comp_cost / comp_hits side effects, but the codec runs as gfx950 kernels.
 // The batch entry points let the sweep (src/list.c:1039-1063) and restore
 // (src/list.c:563-589) callers hand over many pages per launch, and the
-// device-resident API is what bench.py measures.
+// device-resident API is what bench.py measures.  The entry points that start
+// and end in host memory hand their launch to run_host (host_batch.hip).
 //
 // There is no CPU codec in this library: if the HIP device or the gfx950 code
 // object is unavailable every codec entry point returns an error.
@@ -33,14 +34,13 @@
 #include <vector>
 
 #include "engine.h"
+#include "host_batch.h"
 
 #include <immintrin.h>
 
 using namespace tyche;
 
 namespace {
-constexpr int kMaxDevices = 64;
-
 // ------------------------------------------------------------- work counters
 // One pool of device counters per device.  An entry is free, leased (between
 // WorkCounter's constructor and destructor), or released: an event recorded on
@@ -359,20 +359,6 @@ long tyche::knob(const char *name, long dflt) {
 }
 
 namespace {
-// Diagnostic builds only (-DTYCHE_PROFILE, libtyche_codec_prof.so): TYCHE_HOST_DIAG bit 0 makes the
-// host batch report the results without copying the page bytes out (prices the scatter copies).  The
-// product library has no such switch, so a stray setting can never report success without the data
-// (ADVICE r05).
-bool host_diag_no_copy() {
-#ifdef TYCHE_PROFILE
-    return (tyche::knob("HOST_DIAG", 0) & 1) != 0;
-#else
-    return false;
-#endif
-}
-}  // namespace
-
-namespace {
 
 // -1: the host API spreads work over every usable device (the default);
 // >= 0: tyche_set_device pinned the calling thread to that device
@@ -390,36 +376,36 @@ void log_error(const std::string &m) {
     const std::string line = "tyche-engine: " + m + "\n";
     (void)!write(2, line.data(), line.size());
 }
-int fail(const char *what, hipError_t e) {
-    t_error = std::string(what) + ": " + hipGetErrorString(e);
-    log_error(t_error);
-    return TYCHE_E_DEVICE;
-}
-int fail_msg(const std::string &m) {
-    t_error = m;
-    log_error(t_error);
-    return TYCHE_E_DEVICE;
-}
-
-uint64_t now_ns() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
 
 bool device_is_gfx950(int dev) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
     return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
+}  // namespace
 
-// The devices the host API uses when the thread is not pinned: the visible
-// gfx950 devices, the first TYCHE_DEVICES of them when that is set.
-struct DeviceSet {
-    std::vector<int> ids;
-    std::string why;   // empty when ids is non-empty
-};
-const DeviceSet &device_set() {
+// ---- shared with the host pipeline (host_batch.h)
+int tyche::fail(const char *what, hipError_t e) {
+    t_error = std::string(what) + ": " + hipGetErrorString(e);
+    log_error(t_error);
+    return TYCHE_E_DEVICE;
+}
+int tyche::fail_msg(const std::string &m) {
+    t_error = m;
+    log_error(t_error);
+    return TYCHE_E_DEVICE;
+}
+const std::string &tyche::thread_error() { return t_error; }
+void tyche::set_thread_error(const std::string &m) { t_error = m; }
+int tyche::pinned_device() { return t_device; }
+
+uint64_t tyche::now_ns() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
+}
+
+const DeviceSet &tyche::device_set() {
     static DeviceSet &ds = *new DeviceSet([] {
         DeviceSet d;
         int n = 0;
@@ -449,24 +435,8 @@ const DeviceSet &device_set() {
     return ds;
 }
 
-// Restores the calling thread's current device when it goes out of scope: the
-// host entry points switch devices to run a batch, and a caller (a torch rank
-// after set_device, say) must find its own device current afterwards.
-struct DeviceGuard {
-    int saved = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&saved) != hipSuccess) saved = -1;
-    }
-    ~DeviceGuard() {
-        int now = -1;
-        if (saved >= 0 && hipGetDevice(&now) == hipSuccess && now != saved) (void)hipSetDevice(saved);
-    }
-    DeviceGuard(const DeviceGuard &) = delete;
-    DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
 // makes `dev` current on this thread after checking it (cached per device)
-int ensure_device(int dev) {
+int tyche::ensure_device(int dev) {
     static std::atomic<int> ok[kMaxDevices];   // 0 unknown, 1 gfx950, 2 unusable
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
@@ -479,8 +449,7 @@ int ensure_device(int dev) {
     return TYCHE_E_OK;
 }
 
-int rank_device();
-
+namespace {
 // the device for a thread's device-side work: its pinned one, the rank's, else the first of the set
 int current_device(int *dev) {
     if (t_device >= 0 || rank_device() >= 0) {
@@ -559,765 +528,7 @@ inline uint32_t decode_in_cap(const tyche_batch_t &b, uint32_t fallback) {
 // in_cap for an encode batch: the largest page length, 65,535 when per-page lengths come without a maximum
 inline uint32_t encode_in_cap(const tyche_batch_t &b) { return decode_in_cap(b, 65535u); }
 
-// ---------------------------------------------------------------- host batches
-// The Buffer API and the host batch entry points start and end in host memory
-// (tyche's Buffer->data is malloc'd, src/buffer.c:181, 246).  A batch is cut
-// into chunks of ~kChunkBytes of input that flow through a ring of kSlots
-// staging slots, one HIP stream each:
-//
-//   host gather (thread pool memcpy into pinned) -> H2D -> kernel -> D2H -> host scatter
-//
-// so chunk c's gather overlaps chunk c-1's copies and kernel and chunk c-2's
-// scatter; the two copy directions and the kernels of different slots run
-// concurrently.  tyche calls the codec from its compressor pool and its
-// worker threads at once (src/list.c:1051, 572; opts.cpu_count threads,
-// src/options.c:64): the staging contexts are therefore a small per-device pool
-// (TYCHE_HOST_CONTEXTS, default kContextsPerDevice) that a call borrows for its
-// duration, not one per calling thread, so streams and pinned arenas stay
-// bounded however many threads call in.
-struct Arena {
-    void *p = nullptr;
-    void *dp = nullptr;   // host arenas: the device's address of the pinned buffer (zero-copy launches)
-    size_t cap = 0;
-    bool host = false;
-    int grow(size_t need) {
-        if (need <= cap) return TYCHE_E_OK;
-        size_t n = std::max(need, cap * 2);
-        n = (n + 4095) & ~size_t(4095);
-        release();
-        hipError_t e = host ? hipHostMalloc(&p, n, hipHostMallocDefault) : hipMalloc(&p, n);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(host ? "hipHostMalloc" : "hipMalloc", e);
-        }
-        if (host && hipHostGetDevicePointer(&dp, p, 0) != hipSuccess) dp = nullptr;
-        cap = n;
-        return TYCHE_E_OK;
-    }
-    void release() {
-        if (p) {
-            if (host) (void)hipHostFree(p); else (void)hipFree(p);
-        }
-        p = dp = nullptr;
-        cap = 0;
-    }
-};
-
-constexpr int kSlots = 4;   // round 3: 4 x 32 MiB (was 3 x 64 MiB): the host path waited on streams ~30 % of a call
-constexpr size_t kChunkBytes = size_t(32) << 20;
 constexpr size_t kBulkSmallMax = 64;   // pages of up to 65,536 bytes a raw LZ4 host decode batch may hold beside larger ones
-constexpr int kContextsPerDevice = 8;
-
-struct Slot {
-    hipStream_t stream = nullptr;
-    Arena h_in, h_out, h_meta, d_in, d_out, d_meta;
-    size_t first = 0, count = 0;   // pages of the chunk in flight
-    bool busy = false;
-    Slot() { h_in.host = h_out.host = h_meta.host = true; }
-};
-
-struct HostCtx {
-    Slot slot[kSlots];
-    int group = 0;   // hardware-queue group of slot 0's stream (see acquire_ctx)
-    // waits for whatever the slots still hold and forgets it (error paths)
-    void abandon() {
-        for (Slot &s : slot)
-            if (s.busy) {
-                (void)hipStreamSynchronize(s.stream);
-                s.busy = false;
-            }
-    }
-};
-
-struct CtxPool {
-    std::mutex mu;
-    std::condition_variable cv;
-    std::vector<HostCtx *> all, idle;
-    std::vector<int> busy;   // leased contexts per hardware-queue group
-};
-CtxPool *const g_ctx = new CtxPool[kMaxDevices];   // never destroyed (restore dispatchers may run at exit)
-
-// HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default), in
-// creation order; kernels of streams that share a queue run one after the
-// other (tools/probes/hwq.hip: with 24 streams, stream 0 overlaps streams
-// 1-6 but serializes with 7, 11, 15, ...).  Two restore batches (an LZ4 and a
-// zlib one, say) on contexts whose streams share a queue therefore wait for
-// each other.  So a device's contexts are created together, their streams in
-// an order that puts slot s of context i in group (i + s) mod Q -- the three
-// slots of one context on three queues, for the chunk pipeline -- and a call
-// borrows the idle context whose group has the fewest calls running.
-int hw_queues() {
-    static const int q = [] {
-        const char *env = getenv("GPU_MAX_HW_QUEUES");
-        const int v = env ? atoi(env) : 4;
-        return v > 0 ? v : 4;
-    }();
-    return q;
-}
-
-int context_cap() {
-    static const int cap = [] {
-        const char *env = getenv("TYCHE_HOST_CONTEXTS");
-        const int v = env ? atoi(env) : kContextsPerDevice;
-        return v > 0 ? v : kContextsPerDevice;
-    }();
-    return cap;
-}
-
-// creates the device's contexts (under P.mu): stream k created goes to queue
-// group k mod Q, and is given to the (context, slot) pair of that group
-int create_contexts(CtxPool &P) {
-    const int n = context_cap(), Q = hw_queues();
-    std::vector<HostCtx *> cs;
-    for (int i = 0; i < n; i++) {
-        cs.push_back(new HostCtx);
-        cs.back()->group = i % Q;
-    }
-    std::vector<bool> made((size_t)n * kSlots, false);
-    for (int k = 0; k < n * kSlots; k++) {
-        int pick = -1;
-        for (int j = 0; j < n * kSlots && pick < 0; j++)
-            if (!made[j] && ((j / kSlots) + (j % kSlots)) % Q == k % Q) pick = j;
-        for (int j = 0; j < n * kSlots && pick < 0; j++)
-            if (!made[j]) pick = j;
-        made[pick] = true;
-        hipError_t e = hipStreamCreateWithFlags(&cs[pick / kSlots]->slot[pick % kSlots].stream, hipStreamNonBlocking);
-        if (e != hipSuccess) {
-            for (HostCtx *c : cs) {
-                for (Slot &t : c->slot)
-                    if (t.stream) (void)hipStreamDestroy(t.stream);
-                delete c;
-            }
-            return fail("hipStreamCreate", e);
-        }
-    }
-    P.all = cs;
-    P.idle = cs;
-    P.busy.assign((size_t)Q, 0);
-    return TYCHE_E_OK;
-}
-
-// borrows a staging context of device dev (current on this thread); waits while all are busy
-int acquire_ctx(int dev, HostCtx **out) {
-    CtxPool &P = g_ctx[dev];
-    std::unique_lock<std::mutex> g(P.mu);
-    if (P.all.empty()) {
-        const int rc = create_contexts(P);
-        if (rc) return rc;
-    }
-    P.cv.wait(g, [&] { return !P.idle.empty(); });
-    // least-busy group; among equals the most recently released context (its
-    // pinned and device arenas are already grown -- a fresh context pays
-    // hipHostMalloc/hipMalloc for its staging slots on first use)
-    size_t best = P.idle.size() - 1;
-    for (size_t k = best; k-- > 0;)
-        if (P.busy[(size_t)P.idle[k]->group] < P.busy[(size_t)P.idle[best]->group]) best = k;
-    *out = P.idle[best];
-    P.idle.erase(P.idle.begin() + (long)best);
-    P.busy[(size_t)(*out)->group]++;
-    return TYCHE_E_OK;
-}
-void release_ctx(int dev, HostCtx *c) {
-    CtxPool &P = g_ctx[dev];
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        P.busy[(size_t)c->group]--;
-        P.idle.push_back(c);
-    }
-    P.cv.notify_one();
-}
-
-inline size_t up16(size_t x) { return (x + 15) & ~size_t(15); }
-
-// Page copies between malloc'd Buffers and the pinned staging arenas.  The host
-// path is bound by these copies (r03 stage clocks: gather + scatter ~10 of the
-// 15 ms of a 32K-page decompress call), and a plain memcpy of a 16 KiB page
-// reads its destination's lines before writing them (read-for-ownership): three
-// DRAM transfers per byte.  Non-temporal 16-byte stores skip that read; the
-// caller of a pool job fences once at its end (copy_fence) before handing the
-// arena to a DMA or the caller.
-inline void copy_nt(void *dst, const void *src, size_t n) {
-    if (n < 512 || ((uintptr_t)dst & 15u)) {
-        memcpy(dst, src, n);
-        return;
-    }
-    __m128i *d = (__m128i *)dst;
-    const __m128i *p = (const __m128i *)src;
-    size_t k = n >> 6;
-    for (; k; k--, d += 4, p += 4) {
-        const __m128i a = _mm_loadu_si128(p), b = _mm_loadu_si128(p + 1), c = _mm_loadu_si128(p + 2),
-                      e = _mm_loadu_si128(p + 3);
-        _mm_stream_si128(d, a);
-        _mm_stream_si128(d + 1, b);
-        _mm_stream_si128(d + 2, c);
-        _mm_stream_si128(d + 3, e);
-    }
-    const size_t done = n & ~(size_t)63;
-    if (done < n) memcpy((uint8_t *)dst + done, (const uint8_t *)src + done, n - done);
-}
-inline void copy_fence() { _mm_sfence(); }
-
-// A persistent worker pool for the host-side page copies (memcpy of scattered
-// malloc'd pages into and out of pinned staging).  Several callers (one per
-// device of a fanned-out batch, concurrent tyche threads) may run jobs at once:
-// each caller works on its own job and idle workers join whichever job still
-// has ranges left.
-class CopyPool {
-  public:
-    static CopyPool &get() {
-        // never destroyed: its detached workers wait on its condition variable until exit
-        static CopyPool *p = new CopyPool;
-        return *p;
-    }
-    // runs f(i) for i in [0, n), in contiguous ranges, on the pool and the caller
-    template <typename F>
-    void run(size_t n, F f) {
-        if (n < 64 || workers_.empty()) {
-            for (size_t i = 0; i < n; i++) f(i);
-            copy_fence();
-            return;
-        }
-        std::function<void(size_t, size_t)> body = [&f](size_t a, size_t b) {
-            for (size_t i = a; i < b; i++) f(i);
-            copy_fence();   // the job's non-temporal stores are globally visible before it completes
-        };
-        Job j;
-        j.body = &body;
-        j.n = n;
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            jobs_.push_back(&j);
-        }
-        cv_.notify_all();
-        work(j);
-        std::unique_lock<std::mutex> g(mu_);
-        jobs_.erase(std::find(jobs_.begin(), jobs_.end(), &j));   // no worker joins it from now on
-        done_cv_.wait(g, [&] { return j.active == 0; });
-    }
-
-  private:
-    static constexpr size_t kGrain = 32;
-    struct Job {
-        const std::function<void(size_t, size_t)> *body = nullptr;
-        size_t n = 0;
-        std::atomic<size_t> next{0};
-        int active = 0;   // workers inside work(); guarded by mu_
-    };
-    CopyPool() {
-        unsigned t = std::thread::hardware_concurrency();
-        const char *env = getenv("TYCHE_HOST_THREADS");
-        unsigned want = env ? (unsigned)atoi(env) : std::min(16u, t ? t : 1u);
-        for (unsigned i = 1; i < want; i++) workers_.emplace_back([this] { loop(); });
-        for (auto &w : workers_) w.detach();
-    }
-    static void work(Job &j) {
-        for (;;) {
-            const size_t a = j.next.fetch_add(kGrain);
-            if (a >= j.n) break;
-            (*j.body)(a, std::min(j.n, a + kGrain));
-        }
-    }
-    Job *open_job() {   // under mu_
-        for (Job *j : jobs_)
-            if (j->next.load() < j->n) return j;
-        return nullptr;
-    }
-    void loop() {
-        for (;;) {
-            Job *j = nullptr;
-            {
-                // j->next advances outside the lock (callers and workers claim ranges with
-                // fetch_add): pick the job once, in the predicate, and pin it there
-                std::unique_lock<std::mutex> g(mu_);
-                cv_.wait(g, [&] { return (j = open_job()) != nullptr; });
-                j->active++;
-            }
-            work(*j);
-            {
-                std::lock_guard<std::mutex> g(mu_);
-                j->active--;
-            }
-            done_cv_.notify_all();
-        }
-    }
-    std::vector<std::thread> workers_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_cv_;
-    std::vector<Job *> jobs_;
-};
-
-std::atomic<int> g_inflight[kMaxDevices];   // host batches running per device
-
-
-// run_host_batch's direct_out modes (see there)
-enum { kDirectNone = 0, kDirectAlways = 1, kDirectLz4Decode = 2 };
-
-// Host-path stage clocks (diagnostics, tyche_host_profile): ns spent by calling threads waiting for a
-// slot's stream, scattering results, gathering inputs, and enqueuing copies and kernels; bytes gathered
-// and scattered.
-enum { kHpWait, kHpScatter, kHpGather, kHpEnqueue, kHpGatherBytes, kHpScatterBytes, kHpChunks, kHpCount };
-std::atomic<uint64_t> g_hprof[kHpCount];
-struct HpClock {
-    int slot;
-    uint64_t t0;
-    explicit HpClock(int s) : slot(s), t0(now_ns()) {}
-    ~HpClock() { g_hprof[slot] += now_ns() - t0; }
-};
-
-// Moves n host pages through `launch` on device dev, chunk by chunk (see
-// above).  results[i] gets the kernel's per-page result; for results in
-// (0, dst_cap[i]] that many output bytes land in dst[i].  On any failure the
-// context's slots are drained before it goes back to the pool, so a later call
-// never scatters a failed call's chunk.
-// Zero-copy limit: a decompress batch of at most this many bytes (input plus
-// output capacity) skips the device staging buffers -- the kernel reads the
-// gathered streams and the page table from the pinned host arenas and writes
-// results and pages straight back into them.  No H2D/D2H copies (two
-// hipMemcpyAsync calls and two copy kernels each way saved on the restore
-// path's small batches); the kernels stage their input in LDS with 16-byte
-// loads and write whole 16-byte vectors, which PCIe carries well.
-// TYCHE_ZERO_COPY_BYTES=0 turns it off.
-size_t zero_copy_bytes() { return (size_t)std::max(0L, knob("ZERO_COPY_BYTES", 4L << 20)); }
-
-template <typename Launch>
-int run_host_batch(int dev, size_t n, const void *const *src, const uint32_t *src_len, void *const *dst,
-                   const uint32_t *dst_cap, int32_t *results, Launch launch, bool zc_ok = false,
-                   int direct_out = kDirectNone) {
-    DeviceGuard keep;   // the caller's device is current again on every return
-    int rc = ensure_device(dev);
-    if (rc) return rc;
-    struct Inflight {
-        int d;
-        explicit Inflight(int dd) : d(dd) { g_inflight[d]++; }
-        ~Inflight() { g_inflight[d]--; }
-    } inflight(dev);
-    HostCtx *cp = nullptr;
-    if ((rc = acquire_ctx(dev, &cp))) return rc;
-    HostCtx &c = *cp;
-    CopyPool &pool = CopyPool::get();
-    hipError_t e;
-    std::function<void()> before_bail;   // stops the async finisher (below) before the slots are drained
-    auto bail = [&](int r) {
-        if (before_bail) before_bail();
-        c.abandon();
-        release_ctx(dev, cp);
-        return r;
-    };
-
-    // completes the chunk held by slot s: wait for its stream, scatter its outputs
-    auto finish = [&](Slot &S) -> int {
-        if (!S.busy) return TYCHE_E_OK;
-        S.busy = false;
-        {
-            HpClock hc(kHpWait);
-            if ((e = hipStreamSynchronize(S.stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
-        }
-        HpClock hc(kHpScatter);
-        const size_t k = S.count;
-        const uint64_t *m_doff = (const uint64_t *)S.h_meta.p + k;
-        const int32_t *m_res = (const int32_t *)((const uint8_t *)S.h_meta.p + k * 24);
-        const uint8_t *hout = (const uint8_t *)S.h_out.p;
-        const size_t f0 = S.first;
-        std::atomic<uint64_t> moved{0};
-        const bool no_copy = host_diag_no_copy();
-        pool.run(k, [&](size_t j) {
-            const int32_t r = m_res[j];
-            results[f0 + j] = r;
-            if (r > 0 && (uint32_t)r <= dst_cap[f0 + j] && !no_copy) {
-                copy_nt(dst[f0 + j], hout + m_doff[j], (size_t)r);
-                moved.fetch_add((uint64_t)r, std::memory_order_relaxed);
-            }
-        });
-        g_hprof[kHpScatterBytes] += moved.load();
-        g_hprof[kHpChunks]++;
-        return TYCHE_E_OK;
-    };
-
-    if (zc_ok) {
-        size_t in_bytes = 0, out_bytes = 0;
-        uint32_t max_in = 0, max_out = 0;
-        for (size_t j = 0; j < n; j++) {
-            in_bytes += up16(src_len[j]);
-            out_bytes += up16(dst_cap[j]);
-            max_in = std::max(max_in, src_len[j]);
-            max_out = std::max(max_out, dst_cap[j]);
-        }
-        if (in_bytes + out_bytes <= zero_copy_bytes()) {
-            Slot &S = c.slot[0];
-            const size_t meta_bytes = n * 28 + 64;
-            if ((rc = S.h_in.grow(in_bytes + 16)) || (rc = S.h_out.grow(out_bytes + 16)) ||
-                (rc = S.h_meta.grow(meta_bytes)))
-                return bail(rc);
-            if (S.h_in.dp && S.h_out.dp && S.h_meta.dp) {
-                uint64_t *m_soff = (uint64_t *)S.h_meta.p;
-                uint64_t *m_doff = m_soff + n;
-                uint32_t *m_slen = (uint32_t *)(m_doff + n);
-                uint32_t *m_dcap = m_slen + n;
-                int32_t *m_res = (int32_t *)(m_dcap + n);
-                size_t so = 0, dof = 0;
-                for (size_t j = 0; j < n; j++) {
-                    m_soff[j] = so;
-                    m_doff[j] = dof;
-                    m_slen[j] = src_len[j];
-                    m_dcap[j] = dst_cap[j];
-                    so += up16(src_len[j]);
-                    dof += up16(dst_cap[j]);
-                }
-                uint8_t *hin = (uint8_t *)S.h_in.p;
-                {
-                    HpClock hc(kHpGather);
-                    pool.run(n, [&](size_t j) {
-                        if (m_slen[j]) copy_nt(hin + m_soff[j], src[j], m_slen[j]);
-                    });
-                }
-                uint8_t *dm = (uint8_t *)S.h_meta.dp;
-                tyche_batch_t b{};
-                b.count = n;
-                b.src = S.h_in.dp;
-                b.src_offsets = (const uint64_t *)dm;
-                b.src_lengths = (const uint32_t *)(dm + ((uint8_t *)m_slen - (uint8_t *)m_soff));
-                b.max_src_length = max_in;
-                b.dst = S.h_out.dp;
-                b.dst_offsets = (const uint64_t *)(dm + ((uint8_t *)m_doff - (uint8_t *)m_soff));
-                b.dst_capacities = (const uint32_t *)(dm + ((uint8_t *)m_dcap - (uint8_t *)m_soff));
-                b.dst_capacity = max_out;
-                b.results = (int32_t *)(dm + ((uint8_t *)m_res - (uint8_t *)m_soff));
-                S.first = 0;
-                S.count = n;
-                S.busy = true;
-                {
-                    HpClock hc(kHpEnqueue);
-                    if ((e = launch(b, S.stream, true)) != hipSuccess) return bail(fail("kernel launch", e));
-                }
-                S.busy = false;
-                {
-                    HpClock hc(kHpWait);
-                    if ((e = hipStreamSynchronize(S.stream)) != hipSuccess) return bail(fail("hipStreamSynchronize", e));
-                }
-                const uint8_t *hout = (const uint8_t *)S.h_out.p;
-                HpClock hc(kHpScatter);
-                pool.run(n, [&](size_t j) {
-                    const int32_t r = m_res[j];
-                    results[j] = r;
-                    if (r > 0 && (uint32_t)r <= dst_cap[j]) copy_nt(dst[j], hout + m_doff[j], (size_t)r);
-                });
-                release_ctx(dev, cp);
-                return TYCHE_E_OK;
-            }
-        }
-    }
-
-    size_t first = 0;
-    int si = 0;
-    // Async finishing (round 3): with three or more chunks a helper thread waits for each slot's
-    // stream and scatters its results while the caller gathers and enqueues the next chunk -- the
-    // r03 stage clocks had the caller waiting on streams ~25 % of a call, between its copies.
-    // A slot is reused only after the helper has scattered it (S.busy false, under fm).
-    size_t nchunks_est = 0, rem_in = 0, rem_out = 0;   // rem_*: bytes of the batch not yet in a chunk
-    {
-        for (size_t j = 0; j < n; j++) {
-            rem_in += up16(src_len[j]);
-            rem_out += up16(dst_cap[j]);
-        }
-        nchunks_est = (rem_in + rem_out) /
-                      std::max<size_t>(1, (size_t)std::max(1L, knob("HOST_CHUNK_MB", (long)(kChunkBytes >> 20))) << 20);
-    }
-    const bool async = nchunks_est >= 3 && knob("HOST_ASYNC_SCATTER", 1) != 0;
-    std::mutex fm;
-    std::condition_variable fcv;
-    std::vector<int> fq;   // slots to finish, in issue order
-    bool fstop = false;
-    int frc = TYCHE_E_OK;
-    std::string ferr;
-    std::vector<std::thread> fth;
-    auto finish_async = [&](Slot &S) -> int {   // helper thread: sync, scatter, then free the slot
-        hipError_t fe;
-        {
-            HpClock hc(kHpWait);
-            if ((fe = hipStreamSynchronize(S.stream)) != hipSuccess) return fail("hipStreamSynchronize", fe);
-        }
-        HpClock hc(kHpScatter);
-        const size_t k = S.count;
-        const uint64_t *m_doff = (const uint64_t *)S.h_meta.p + k;
-        const int32_t *m_res = (const int32_t *)((const uint8_t *)S.h_meta.p + k * 24);
-        const uint8_t *hout = (const uint8_t *)S.h_out.p;
-        const size_t f0 = S.first;
-        std::atomic<uint64_t> moved{0};
-        const bool no_copy = host_diag_no_copy();
-        pool.run(k, [&](size_t j) {
-            const int32_t r = m_res[j];
-            results[f0 + j] = r;
-            if (r > 0 && (uint32_t)r <= dst_cap[f0 + j] && !no_copy) {
-                copy_nt(dst[f0 + j], hout + m_doff[j], (size_t)r);
-                moved.fetch_add((uint64_t)r, std::memory_order_relaxed);
-            }
-        });
-        g_hprof[kHpScatterBytes] += moved.load();
-        g_hprof[kHpChunks]++;
-        return TYCHE_E_OK;
-    };
-    // HOST_FINISHERS helpers (default 1), each taking the next queued slot (chunks go to disjoint
-    // destinations, so their scatters may run in any order, on the shared copy pool).  Round 5: a
-    // second and third helper, so that one chunk's scatter overlaps the next one's wait, did not
-    // move decompress (32K pages, best of 5 interleaved: 34.2 / 33.7 / 31.7 GiB/s for 1 / 2 / 3,
-    // profiles/r05_host_probe.jsonl).
-    const int nfin = async ? (int)std::min(4L, std::max(1L, knob("HOST_FINISHERS", 1))) : 0;
-    for (int h = 0; h < nfin; h++) {
-        fth.emplace_back([&] {
-            for (;;) {
-                int idx;
-                {
-                    std::unique_lock<std::mutex> g(fm);
-                    fcv.wait(g, [&] { return !fq.empty() || fstop || frc != TYCHE_E_OK; });
-                    if (fq.empty() || frc != TYCHE_E_OK) return;
-                    idx = fq.front();
-                    fq.erase(fq.begin());
-                }
-                const int r = finish_async(c.slot[idx]);
-                std::lock_guard<std::mutex> g(fm);
-                if (r) {
-                    if (frc == TYCHE_E_OK) {
-                        frc = r;
-                        ferr = t_error;   // the helper's thread-local message
-                    }
-                    fcv.notify_all();
-                    return;
-                }
-                c.slot[idx].busy = false;
-                fcv.notify_all();
-            }
-        });
-    }
-    auto stop_helper = [&] {
-        if (fth.empty()) return;
-        {
-            std::lock_guard<std::mutex> g(fm);
-            fstop = true;
-        }
-        fcv.notify_all();
-        for (auto &t : fth) t.join();
-        fth.clear();
-    };
-    struct HelperJoin {   // every return path stops the helper (bail() does so before draining the streams)
-        std::function<void()> f;
-        ~HelperJoin() { f(); }
-    } helper_join{stop_helper};
-    before_bail = stop_helper;
-    auto async_fail = [&]() -> int {
-        stop_helper();
-        t_error = ferr;
-        return frc;
-    };
-    // chunks hold ~chunk_bytes of input AND of output capacity: a decompress batch's
-    // output is ~2.6x its input, so cutting by input alone made 3 chunks of 170 MiB
-    // of D2H each out of a 32K-page batch, too few to overlap the two copy directions
-    const size_t chunk_bytes = (size_t)std::max(1L, knob("HOST_CHUNK_MB", (long)(kChunkBytes >> 20))) << 20;
-    // ramp (HOST_RAMP, default on): the first and the last chunk are a quarter chunk, so the
-    // pipeline fills (H2D + kernel before the first D2H) and drains (the last D2H + scatter,
-    // which nothing overlaps) on small chunks
-    const bool ramp = knob("HOST_RAMP", 1) != 0 && nchunks_est >= 3;
-    const size_t quarter = std::max<size_t>(chunk_bytes / 4, 1u << 20);
-    size_t nchunk = 0;
-    while (first < n) {
-        // ---- chunk [first, last)
-        size_t limit = chunk_bytes;
-        if (ramp) {
-            const size_t rem = std::max(rem_in, rem_out);
-            if (nchunk == 0) limit = quarter;
-            else if (rem <= chunk_bytes + quarter && rem > quarter) limit = rem - quarter;
-        }
-        nchunk++;
-        size_t last = first, in_bytes = 0, out_bytes = 0;
-        uint32_t max_in = 0, max_out = 0;
-        while (last < n && (last == first || (in_bytes + up16(src_len[last]) <= limit &&
-                                              out_bytes + up16(dst_cap[last]) <= limit))) {
-            in_bytes += up16(src_len[last]);
-            out_bytes += up16(dst_cap[last]);
-            max_in = std::max(max_in, src_len[last]);
-            max_out = std::max(max_out, dst_cap[last]);
-            last++;
-        }
-        const size_t k = last - first;
-        rem_in -= in_bytes;
-        rem_out -= out_bytes;
-        Slot &S = c.slot[si];
-        if (async) {   // the helper has scattered the slot's previous chunk
-            std::unique_lock<std::mutex> g(fm);
-            fcv.wait(g, [&] { return !S.busy || frc != TYCHE_E_OK; });
-            if (frc != TYCHE_E_OK) {
-                g.unlock();
-                return bail(async_fail());
-            }
-        } else if ((rc = finish(S))) {
-            return bail(rc);   // the slot's previous chunk
-        }
-        // meta layout: soff[k] u64, doff[k] u64, slen[k] u32, dcap[k] u32, res[k] i32
-        const size_t meta_bytes = k * 28 + 64;
-        if ((rc = S.h_in.grow(in_bytes + 16)) || (rc = S.h_out.grow(out_bytes + 16)) ||
-            (rc = S.h_meta.grow(meta_bytes)) || (rc = S.d_in.grow(in_bytes + 16)) ||
-            (rc = S.d_out.grow(out_bytes + 16)) || (rc = S.d_meta.grow(meta_bytes)))
-            return bail(rc);
-        uint64_t *m_soff = (uint64_t *)S.h_meta.p;
-        uint64_t *m_doff = m_soff + k;
-        uint32_t *m_slen = (uint32_t *)(m_doff + k);
-        uint32_t *m_dcap = m_slen + k;
-        int32_t *m_res = (int32_t *)(m_dcap + k);
-        size_t so = 0, dof = 0;
-        for (size_t j = 0; j < k; j++) {
-            m_soff[j] = so;
-            m_doff[j] = dof;
-            m_slen[j] = src_len[first + j];
-            m_dcap[j] = dst_cap[first + j];
-            so += up16(src_len[first + j]);
-            dof += up16(dst_cap[first + j]);
-        }
-        uint8_t *hin = (uint8_t *)S.h_in.p;
-        {
-            HpClock hc(kHpGather);
-            pool.run(k, [&](size_t j) {
-                if (m_slen[j]) copy_nt(hin + m_soff[j], src[first + j], m_slen[j]);
-            });
-            g_hprof[kHpGatherBytes] += so;
-        }
-        HpClock enq(kHpEnqueue);
-        // ---- H2D -> kernel -> D2H on the slot's stream
-        uint8_t *dmeta = (uint8_t *)S.d_meta.p;
-        const size_t head_bytes = (uint8_t *)m_res - (uint8_t *)m_soff;
-        S.first = first;
-        S.count = k;
-        {
-            std::lock_guard<std::mutex> g(fm);
-            S.busy = true;   // from the first enqueued copy on, the slot must be drained on failure
-        }
-        if ((e = hipMemcpyAsync(dmeta, S.h_meta.p, head_bytes, hipMemcpyHostToDevice, S.stream)) != hipSuccess)
-            return bail(fail("hipMemcpyAsync(meta)", e));
-        if (so && (e = hipMemcpyAsync(S.d_in.p, hin, so, hipMemcpyHostToDevice, S.stream)) != hipSuccess)
-            return bail(fail("hipMemcpyAsync(in)", e));
-        tyche_batch_t b{};
-        b.count = k;
-        b.src = S.d_in.p;
-        b.src_offsets = (const uint64_t *)dmeta;
-        b.src_lengths = (const uint32_t *)(dmeta + ((uint8_t *)m_slen - (uint8_t *)m_soff));
-        b.max_src_length = max_in;
-        // direct_out: the kernel writes its results straight into the pinned arena over PCIe, as
-        // posted writes that overlap its own work, and no D2H of the arena follows.  LZ4 compress
-        // (kDirectAlways): only the compressed bytes cross the link -- a D2H of the arena would move
-        // every page's full capacity (16 KiB+ per 16 KiB page at ratio 2.6).  LZ4 decompress
-        // (kDirectLz4Decode): the jump and wave decoders write each page once, whole, from LDS; the
-        // lane decoder (chunks of >= kLaneMin pages) reads its own output back, so it keeps the D2H;
-        // TYCHE_HOST_DIRECT_DECODE_MAX: chunks of more pages than this stage through HBM too.  The
-        // choice is made once here and handed to the launch (host_dst), so a knob changed meanwhile
-        // cannot put the lane decoder on a host destination.
-        const bool direct = S.h_out.dp != nullptr &&
-                            (direct_out == kDirectAlways ||
-                             (direct_out == kDirectLz4Decode && !lz4_lane_decode_wanted(k, max_in, max_out) &&
-                              (long)k <= knob("HOST_DIRECT_DECODE_MAX", 1L << 30)));
-        b.dst = direct ? S.h_out.dp : S.d_out.p;
-        b.dst_offsets = (const uint64_t *)(dmeta + ((uint8_t *)m_doff - (uint8_t *)m_soff));
-        b.dst_capacities = (const uint32_t *)(dmeta + ((uint8_t *)m_dcap - (uint8_t *)m_soff));
-        b.dst_capacity = max_out;
-        b.results = (int32_t *)(dmeta + head_bytes);
-        if ((e = launch(b, S.stream, direct)) != hipSuccess) return bail(fail("kernel launch", e));
-        if ((e = hipMemcpyAsync(m_res, b.results, k * 4, hipMemcpyDeviceToHost, S.stream)) != hipSuccess)
-            return bail(fail("hipMemcpyAsync(results)", e));
-        if (dof && !direct && (e = hipMemcpyAsync(S.h_out.p, S.d_out.p, dof, hipMemcpyDeviceToHost, S.stream)) != hipSuccess)
-            return bail(fail("hipMemcpyAsync(out)", e));
-        if (async) {
-            std::lock_guard<std::mutex> g(fm);
-            fq.push_back(si);
-            fcv.notify_all();
-        }
-        first = last;
-        si = (si + 1) % kSlots;
-    }
-    if (async) {   // the helper drains the queue, then stops
-        stop_helper();
-        if (frc != TYCHE_E_OK) {
-            t_error = ferr;
-            return bail(frc);
-        }
-        release_ctx(dev, cp);
-        return TYCHE_E_OK;
-    }
-    // drain in issue order
-    for (int j = 0; j < kSlots; j++)
-        if ((rc = finish(c.slot[(si + j) % kSlots]))) return bail(rc);
-    release_ctx(dev, cp);
-    return TYCHE_E_OK;
-}
-
-// minimum input bytes per device before a host batch is split across devices
-uint64_t fanout_min_bytes() { return (uint64_t)std::max(0L, knob("FANOUT_MIN_BYTES", 64L << 20)); }
-
-// A process launched one per GPU (torch.distributed.run sets LOCAL_RANK and
-// LOCAL_WORLD_SIZE) keeps its host work on its own device -- LOCAL_RANK modulo
-// the visible devices, torch's convention, whichever thread calls.  Only
-// LOCAL_RANK engages it (a launcher that sets WORLD_SIZE alone gets the
-// fan-out, not device 0), a LOCAL_WORLD_SIZE of 1 does not (the node's only
-// process may use every device), and TYCHE_DEVICES / TYCHE_DEVICE_IDS or the
-// RANK_PIN knob (0, at any time through tyche_set_knob) turn it off, e.g. for a
-// helper process that inherited a worker's environment.  -1: not pinned.
-int rank_device() {
-    static const int d = [] {
-        if (getenv("TYCHE_DEVICES") || getenv("TYCHE_DEVICE_IDS")) return -1;
-        const char *lr = getenv("LOCAL_RANK"), *lw = getenv("LOCAL_WORLD_SIZE");
-        if (!lr || !*lr || (lw && atoi(lw) == 1)) return -1;
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return -1;
-        return std::max(0, atoi(lr)) % n;
-    }();
-    return d >= 0 && knob("RANK_PIN", 1) != 0 ? d : -1;
-}
-
-// the device with the fewest host batches in flight (ties rotate)
-int pick_device(const std::vector<int> &ids) {
-    static std::atomic<unsigned> rot{0};
-    const unsigned r = rot++;
-    int best = ids[r % ids.size()];
-    for (size_t k = 0; k < ids.size(); k++) {
-        const int d = ids[(r + k) % ids.size()];
-        if (g_inflight[d].load() < g_inflight[best].load()) best = d;
-    }
-    return best;
-}
-
-// Host batch over the calling thread's devices: its pinned device, or the
-// device set.  Batches of at least two parts' worth of input
-// (tyche_plan_split) are cut into contiguous page ranges of about equal input
-// bytes, one per device, run concurrently; smaller ones go whole to the least
-// busy device, so concurrent small calls (tyche's per-page compressor pool and
-// restores) spread over all devices.
-template <typename Launch>
-int run_host(size_t n, const void *const *src, const uint32_t *src_len, void *const *dst, const uint32_t *dst_cap,
-             int32_t *results, Launch launch, bool zc_ok = false, int direct_out = kDirectNone) {
-    if (t_device >= 0) return run_host_batch(t_device, n, src, src_len, dst, dst_cap, results, launch, zc_ok, direct_out);
-    if (rank_device() >= 0)   // one process per GPU: its own device only
-        return run_host_batch(rank_device(), n, src, src_len, dst, dst_cap, results, launch, zc_ok, direct_out);
-    const DeviceSet &ds = device_set();
-    if (ds.ids.empty()) return fail_msg(ds.why);
-    std::vector<size_t> cuts(ds.ids.size() + 1);
-    const size_t parts = tyche_plan_split(n, src_len, (int)ds.ids.size(), fanout_min_bytes(), cuts.data());
-    if (parts <= 1)
-        return run_host_batch(pick_device(ds.ids), n, src, src_len, dst, dst_cap, results, launch, zc_ok, direct_out);
-    std::vector<int> rcs(parts, TYCHE_E_OK);
-    std::vector<std::string> errs(parts);
-    std::vector<std::thread> th;
-    auto part = [&](size_t p) {
-        const size_t a = cuts[p], m = cuts[p + 1] - cuts[p];
-        rcs[p] = run_host_batch(ds.ids[p], m, src + a, src_len + a, dst + a, dst_cap + a, results + a, launch, zc_ok,
-                                direct_out);
-        if (rcs[p]) errs[p] = t_error;
-    };
-    for (size_t p = 1; p < parts; p++) th.emplace_back(part, p);
-    part(0);
-    for (auto &t : th) t.join();
-    for (size_t p = 0; p < parts; p++)
-        if (rcs[p]) {
-            t_error = errs[p];
-            return rcs[p];
-        }
-    return TYCHE_E_OK;
-}
 
 // ------------------------------------------------------ shared LZ4 dictionary
 // A handle is immutable after creation: the bytes, the encoder's dictionary table and the device
@@ -1668,9 +879,7 @@ extern "C" {
 
 // ------------------------------------------------------------------ runtime
 int tyche_host_profile(uint64_t *out, int n) {
-    const int k = std::min(n, (int)kHpCount);
-    for (int i = 0; i < k; i++) out[i] = g_hprof[i].exchange(0);
-    return k;
+    return host_profile_read(out, n);
 }
 
 int tyche_set_knob(const char *name, long value) {
