@@ -304,8 +304,9 @@ uint64_t tyche_pack_plan(size_t n, const int32_t *results, uint32_t max_length, 
  * Without a dictionary (tyche_lz4_use_dict never called or given NULL, no
  * TYCHE_LZ4_DICT, and the plain tyche_*_batch calls) nothing changes: the kernels
  * launched, the bytes and the results are the same.  LZ4_EXACT=1 and a dictionary
- * do not combine: a compress call that has both is TYCHE_E_BAD_ARGS.  zlib and
- * zstd ignore all of this.
+ * do not combine: a compress call that has both is TYCHE_E_BAD_ARGS.  zlib
+ * ignores all of this; zstd has calls and a process-wide slot of its own for the
+ * same handle ("zstd with a shared dictionary" below), which nothing here touches.
  *
  * TYCHE_LZ4_DICT=<file> in the environment: the file's bytes become the
  * process-wide dictionary at the first LZ4 host-path call.  A file that is
@@ -333,6 +334,70 @@ int tyche_lz4_use_dict(const tyche_lz4_dict_t *d);
 uint32_t tyche_lz4_dict_bytes(const tyche_lz4_dict_t *d, void *out, uint32_t cap);
 /* a new reference to the process-wide dictionary (tyche_lz4_dict_destroy drops it), or NULL */
 tyche_lz4_dict_t *tyche_lz4_current_dict(void);
+
+/* ---- zstd with a shared dictionary ---------------------------------------- */
+/* The handle is the LZ4 one: a dictionary's bytes are raw content for both codecs, so a handle
+ * made by tyche_lz4_dict_create or by the trainer serves zstd as it is (tyche_dict_t is the
+ * codec-neutral name of the type).  What the reference does with such bytes is the contract
+ * (ZSTD_compress_usingDict / ZSTD_decompress_usingDict of its zstd 1.1.2, raw-content mode):
+ *
+ * The window.  A dictionary of D bytes followed by a page of L bytes is one window.  The compressed
+ * page is an ordinary zstd frame -- single segment, content size, no dictionary ID, no checksum: the
+ * header the engine always writes, and nothing in it says that a dictionary is needed -- whose
+ * offsets may reach back as far as the first dictionary byte (offset <= position + D; one more is
+ * the error it is to the reference, zstd_decompress.c:831).  The repeat offsets start at {1, 4, 8} as
+ * always.  Compress results are the plain encoder's: the size, or 0 when the frame does not fit the
+ * capacity; nothing is written at or past the capacity; src_len == 0 as without a dictionary;
+ * INT32_MIN above the launch's declared maximum; never longer than tyche_compress_bound; the bytes
+ * depend on the page and the dictionary alone (not on the batch, its size or its layout).
+ * Decompress results are ZSTD_decompress_usingDict's: the decoded size, or a negative value wherever
+ * ZSTD_isError holds; INT32_MIN above the launch's maximum (dst_capacity, or a stream longer than the
+ * declared max_src_length).  The encoder matches against the dictionary's last D & ~63 bytes (a
+ * dictionary below 64 bytes gives the bytes of a plain frame from the same parse); the decoder
+ * honours all D.  A frame written with a dictionary needs it to be restored: the plain decoders and
+ * ZSTD_decompress return an error for it as soon as a match reaches the dictionary.  There is no
+ * checksum, so a wrong dictionary of any length gives the right size and wrong bytes (or an error),
+ * exactly as LZ4's does -- keep the dictionary with the pages it wrote.
+ *
+ * Reach.  As for LZ4: the dictionary applies to a page when L + D <= 65536.  Device-resident calls:
+ * a compress launch whose declared maximum (src_length, or max_src_length beside src_lengths; 0
+ * there still means 65535) plus D exceeds 65536, and a decompress launch whose dst_capacity plus D
+ * does, is TYCHE_E_BAD_ARGS before any device call, with the rule and both numbers in
+ * tyche_last_error().  Host entry points (Buffer API, tyche_buffers_*, host batches, restore queue,
+ * multi-device fan-out) with a process-wide zstd dictionary (tyche_zstd_use_dict, or TYCHE_ZSTD_DICT
+ * below) apply the rule per page -- compress to src_lengths[i], decompress to dst_capacities[i]; a
+ * page outside the reach takes the path, and gets the bytes, it has without a dictionary; a batch
+ * that mixes the classes runs as two launches over the same batch.  As for LZ4, a raw
+ * tyche_decompress_host caller must pass the page length as the capacity, as Buffers do, or a
+ * dictionary frame may land on the plain decoder and get its error verdict -- a failed restore, never
+ * wrong bytes.
+ *
+ * Structured dictionaries.  Bytes that begin with 37 A4 30 EC (ZSTD_DICT_MAGIC) are a structured
+ * (entropy-table) dictionary to the reference, which this engine does not implement: a handle of at
+ * least 4 bytes that begins so is TYCHE_E_BAD_ARGS from every call below, with "structured
+ * dictionaries are not supported" in tyche_last_error().  The LZ4 calls keep accepting such a handle.
+ *
+ * One kernel decodes every batch size (one wave per page, the dictionary in LDS in front of the
+ * window); the split multi-pass decoder of large plain batches has no dictionary variant, and the
+ * encoder always runs its four passes (DESIGN.md 3.4a has what large batches pay for that).
+ *
+ * The process-wide zstd dictionary is a slot of its own: tyche_lz4_use_dict and the TYCHE_LZ4_DICT*
+ * variables do not touch it, and it does not touch LZ4.  Without one (tyche_zstd_use_dict never
+ * called or given NULL, no TYCHE_ZSTD_DICT, and the plain tyche_*_batch calls) nothing changes: the
+ * kernels launched, the bytes and the results are the same.  compressor_level stays ignored.
+ *
+ * TYCHE_ZSTD_DICT=<file> in the environment: the file's bytes become the process-wide zstd
+ * dictionary at the first zstd host-path call.  A file that is unreadable, empty, longer than
+ * TYCHE_LZ4_DICT_MAX or structured makes every zstd host call fail with TYCHE_E_BAD_ARGS and the
+ * reason; it is never silently ignored.  A tyche_zstd_use_dict call replaces whatever it named. */
+typedef tyche_lz4_dict_t tyche_dict_t;   /* the same handle, for both codecs */
+/* device-resident batches, same tyche_batch_t and result rules as tyche_*_batch */
+int tyche_zstd_compress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream);
+int tyche_zstd_decompress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream);
+/* process-wide zstd dictionary of the host entry points; NULL removes it.  Holds a reference of its own. */
+int tyche_zstd_use_dict(const tyche_dict_t *d);
+/* a new reference to the process-wide zstd dictionary (tyche_lz4_dict_destroy drops it), or NULL */
+tyche_dict_t *tyche_zstd_current_dict(void);
 
 /* ---- training a dictionary from sample pages ------------------------------ */
 /* The trainer picks the 128-byte segments of the sample pages whose 8-byte keys occur in the most

@@ -30,12 +30,18 @@ lengths, ``decompress_packed`` decodes from them, ``compress_pages_packed`` does
 compress + append a chunk of rows at a time.  A store's state is two int64 words
 on the device, ``{used, wanted}``; the device decides whether an append fits.
 
-Shared dictionary (LZ4 only): ``dictionary=Lz4Dict(bytes)`` makes the dictionary
-and each row one LZ4 window -- the blocks are what
-``LZ4_decompress_safe_usingDict`` restores, and need the same dictionary to be
-decoded.  Row length (capacity, when decoding) plus dictionary may not exceed
-65,536 bytes.  ``Lz4Dict.train(pages, length)`` makes one from sample pages on
-the GPU; ``Lz4Dict.data`` returns a dictionary's bytes.
+Shared dictionary (LZ4 and zstd): ``dictionary=Dictionary(bytes)`` makes the
+dictionary and each row one window.  LZ4: the blocks are what
+``LZ4_decompress_safe_usingDict`` restores.  zstd: the bytes are a raw-content
+dictionary, the frames what ``ZSTD_decompress_usingDict`` restores (bytes that
+begin with zstd's dictionary magic 37 A4 30 EC are refused: structured
+dictionaries are not supported).  Either way the same dictionary is needed to
+decode, and row length (capacity, when decoding) plus dictionary may not exceed
+65,536 bytes.  zlib has no dictionary (``ValueError``).  ``Dictionary`` is the
+codec-neutral name of ``Lz4Dict``: one handle serves both codecs.
+``Lz4Dict.train(pages, length)`` makes one from sample pages on the GPU;
+``Lz4Dict.data`` returns a dictionary's bytes.  ``use_zstd_dict(d)`` installs
+one for the host entry points' zstd calls (``None`` removes it).
 """
 from __future__ import annotations
 
@@ -44,7 +50,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import LZ4_COMPRESSOR_ID
+from ._lib import LZ4_COMPRESSOR_ID, ZSTD_COMPRESSOR_ID
 
 SLOT_ALIGN = 128
 
@@ -74,8 +80,9 @@ def _check_pages(t: torch.Tensor, name: str) -> None:
 
 
 class Lz4Dict:
-    """A shared LZ4 dictionary (tyche_lz4_dict_create): 1..LZ4_DICT_MAX bytes, copied, immutable.
-    The engine uploads it to a device the first time a launch there uses it."""
+    """A shared dictionary (tyche_lz4_dict_create): 1..LZ4_DICT_MAX bytes, copied, immutable, for the
+    LZ4 and the zstd calls alike (``Dictionary`` is the same class).  The engine uploads it to a
+    device the first time a launch there uses it."""
 
     def __init__(self, data: bytes):
         data = bytes(data)
@@ -140,12 +147,26 @@ class Lz4Dict:
             pass
 
 
+Dictionary = Lz4Dict   # the codec-neutral name
+
+
+def use_zstd_dict(dictionary: Lz4Dict | None) -> None:
+    """Installs ``dictionary`` as the process-wide zstd dictionary of the host entry points
+    (tyche_zstd_use_dict); ``None`` removes it.  The LZ4 slot is not touched."""
+    _lib.check(_lib.load().tyche_zstd_use_dict(dictionary.handle if dictionary is not None else None),
+               "tyche_zstd_use_dict")
+
+
 def _compress_call(compressor_id: int, level: int, b, stream: int, dictionary) -> None:
     if dictionary is None:
         _lib.check(_lib.load().tyche_compress_batch(compressor_id, level, ctypes.byref(b), stream), "tyche_compress_batch")
         return
+    if compressor_id == ZSTD_COMPRESSOR_ID:
+        _lib.check(_lib.load().tyche_zstd_compress_batch_dict(dictionary.handle, ctypes.byref(b), stream),
+                   "tyche_zstd_compress_batch_dict")
+        return
     if compressor_id != LZ4_COMPRESSOR_ID:
-        raise ValueError("dictionary= is an LZ4 feature")
+        raise ValueError("dictionary= is an LZ4 and zstd feature")
     _lib.check(_lib.load().tyche_lz4_compress_batch_dict(dictionary.handle, ctypes.byref(b), stream),
                "tyche_lz4_compress_batch_dict")
 
@@ -154,8 +175,12 @@ def _decompress_call(compressor_id: int, b, stream: int, dictionary) -> None:
     if dictionary is None:
         _lib.check(_lib.load().tyche_decompress_batch(compressor_id, ctypes.byref(b), stream), "tyche_decompress_batch")
         return
+    if compressor_id == ZSTD_COMPRESSOR_ID:
+        _lib.check(_lib.load().tyche_zstd_decompress_batch_dict(dictionary.handle, ctypes.byref(b), stream),
+                   "tyche_zstd_decompress_batch_dict")
+        return
     if compressor_id != LZ4_COMPRESSOR_ID:
-        raise ValueError("dictionary= is an LZ4 feature")
+        raise ValueError("dictionary= is an LZ4 and zstd feature")
     _lib.check(_lib.load().tyche_lz4_decompress_batch_dict(dictionary.handle, ctypes.byref(b), stream),
                "tyche_lz4_decompress_batch_dict")
 

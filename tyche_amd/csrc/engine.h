@@ -139,6 +139,20 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);
 hipError_t launch_zstd_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
+// zstd with a shared raw-content dictionary (zstd_encode.hip, zstd_decode.hip): dictionary + page is
+// one window of at most 65,536 bytes, the frame an ordinary one whose offsets may reach into the
+// dictionary (ZSTD_compress_usingDict / ZSTD_decompress_usingDict).  The handle and its device image
+// are the LZ4 dictionary's (Lz4DictDev: raw bytes are codec-agnostic); the encoder also takes the
+// handle's seeded table, zstd_dict_seed_bytes() bytes that zstd_dict_seed_table computes on the host
+// from the dictionary's last d.enc_len bytes (engine.hip builds and uploads it at the handle's first
+// zstd compress on a device).  per_page as for LZ4: pages beyond the reach are skipped, their results
+// left alone; else in_cap / out_cap + dlen must not exceed the window.
+size_t zstd_dict_seed_bytes();
+void zstd_dict_seed_table(const uint8_t *tail, uint32_t n, void *table_out);
+hipError_t launch_zstd_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, const void *seed,
+                                   bool per_page, hipStream_t s);
+hipError_t launch_zstd_decode_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &d,
+                                   bool per_page, hipStream_t s);
 // Dynamic page assignment.  The codec kernels run one-wave workgroups that loop
 // over pages; when a CU holds a number of waves that is not a multiple of its 4
 // SIMDs, the waves sharing a SIMD run slower than the lone ones, and static

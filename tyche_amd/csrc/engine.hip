@@ -546,6 +546,10 @@ struct tyche_lz4_dict {
     std::vector<uint8_t> image;   // dec (dpad) | table (8 KiB) | enc (16 x enc_stride)
     std::mutex mu;
     uint8_t *dev[kMaxDevices] = {};
+    // the zstd encoder's seeded table (engine.h: zstd_dict_seed_table), built at the handle's first zstd
+    // compress and uploaded to a device at its first one there: LZ4-only users pay nothing for it
+    std::vector<uint8_t> zseed;
+    uint8_t *zdev[kMaxDevices] = {};
 };
 namespace {
 constexpr size_t kDictTableBytes = 4096 * sizeof(uint16_t);
@@ -562,7 +566,10 @@ void dict_release(const tyche_lz4_dict *cd) {
     if (!d || d->refs.fetch_sub(1) != 1) return;
     DeviceGuard keep;
     for (int i = 0; i < kMaxDevices; i++)
-        if (d->dev[i] && hipSetDevice(i) == hipSuccess) (void)hipFree(d->dev[i]);
+        if ((d->dev[i] || d->zdev[i]) && hipSetDevice(i) == hipSuccess) {
+            if (d->dev[i]) (void)hipFree(d->dev[i]);
+            if (d->zdev[i]) (void)hipFree(d->zdev[i]);
+        }
     delete d;
 }
 
@@ -594,6 +601,35 @@ int dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, hipError_t *why = 
     out->dpad = d->dpad;
     out->enc_len = d->enc_len;
     out->enc_stride = d->enc_stride;
+    return TYCHE_E_OK;
+}
+
+// the handle's image and the zstd encoder's seeded table on the current device
+int zdict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, const void **seed, hipError_t *why = nullptr) {
+    if (int rc = dict_on_device(cd, out, why)) return rc;
+    tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess || dev < 0 || dev >= kMaxDevices) return (why ? (void)(*why = hipErrorInvalidDevice) : (void)0), fail_msg("selected device out of range");
+    std::lock_guard<std::mutex> g(d->mu);
+    if (d->zseed.empty()) {
+        d->zseed.resize(zstd_dict_seed_bytes());
+        zstd_dict_seed_table(d->image.data() + (d->dpad - d->enc_len), d->enc_len, d->zseed.data());
+    }
+    if (!d->zdev[dev]) {
+        uint8_t *p = nullptr;
+        if ((e = hipMalloc((void **)&p, d->zseed.size())) != hipSuccess) {
+            if (why) *why = e;
+            return fail("hipMalloc(dictionary table)", e);
+        }
+        if ((e = hipMemcpy(p, d->zseed.data(), d->zseed.size(), hipMemcpyHostToDevice)) != hipSuccess) {
+            (void)hipFree(p);
+            if (why) *why = e;
+            return fail("hipMemcpy(dictionary table)", e);
+        }
+        d->zdev[dev] = p;
+    }
+    *seed = d->zdev[dev];
     return TYCHE_E_OK;
 }
 
@@ -780,6 +816,13 @@ struct DictUploadNote {
         if (msg.empty()) msg = t_error;
         return why;
     }
+    hipError_t upload(const tyche_lz4_dict *d, Lz4DictDev *img, const void **seed) {
+        hipError_t why = hipErrorUnknown;
+        if (zdict_on_device(d, img, seed, &why) == TYCHE_E_OK) return hipSuccess;
+        std::lock_guard<std::mutex> g(mu);
+        if (msg.empty()) msg = t_error;
+        return why;
+    }
     int finish(int rc) {
         if (rc != TYCHE_E_OK && !msg.empty()) {
             t_error = msg;
@@ -792,10 +835,79 @@ int dict_exact_conflict() {
     t_error = "LZ4_EXACT=1 and an LZ4 dictionary do not combine: exact mode promises LZ4_compress_default's bytes";
     return TYCHE_E_BAD_ARGS;
 }
-int dict_reach_error(const char *what, uint32_t cap, uint32_t dlen) {
-    t_error = std::string("LZ4 dictionary reach: ") + what + " (" + std::to_string(cap) + ") plus the dictionary (" +
+int dict_reach_error(const char *what, uint32_t cap, uint32_t dlen, const char *codec = "LZ4") {
+    t_error = std::string(codec) + " dictionary reach: " + what + " (" + std::to_string(cap) + ") plus the dictionary (" +
               std::to_string(dlen) + " bytes) exceeds 65536";
     return TYCHE_E_BAD_ARGS;
+}
+
+// ---- zstd with the same handle.  The bytes are raw content for both codecs; what zstd adds is a
+// rule (bytes that begin with ZSTD_DICT_MAGIC would be a structured dictionary to the reference,
+// which this engine does not implement: refused, never read as raw content) and a process-wide slot
+// of its own, which neither tyche_lz4_use_dict nor the TYCHE_LZ4_DICT* variables touch.
+bool zdict_structured(const tyche_lz4_dict *d) {
+    static const uint8_t magic[4] = {0x37, 0xA4, 0x30, 0xEC};
+    return d->len >= 4u && memcmp(d->image.data() + (d->dpad - d->len), magic, 4) == 0;
+}
+int zdict_structured_error() {
+    t_error = "zstd dictionary: the bytes begin with ZSTD_DICT_MAGIC (37 A4 30 EC), a structured (entropy-table) "
+              "dictionary; structured dictionaries are not supported, only raw content";
+    return TYCHE_E_BAD_ARGS;
+}
+struct ZDictSlot {
+    std::mutex mu;
+    const tyche_lz4_dict *d = nullptr;
+    bool env_done = false;
+    std::string env_error;   // TYCHE_ZSTD_DICT named a file that cannot serve: every zstd host call fails with it
+};
+ZDictSlot &zdict_slot() {
+    static ZDictSlot &s = *new ZDictSlot();   // never destroyed, as dict_slot()
+    return s;
+}
+// TYCHE_ZSTD_DICT=<file>, read once (slot locked)
+void zdict_env_locked(ZDictSlot &S) {
+    if (S.env_done) return;
+    S.env_done = true;
+    const char *path = getenv("TYCHE_ZSTD_DICT");
+    if (!path || !*path) return;
+    std::vector<uint8_t> buf(TYCHE_LZ4_DICT_MAX + 1u);
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+        S.env_error = std::string("TYCHE_ZSTD_DICT: cannot read ") + path;
+        return;
+    }
+    const size_t n = fread(buf.data(), 1, buf.size(), f);
+    fclose(f);
+    if (n == 0 || n > TYCHE_LZ4_DICT_MAX) {
+        S.env_error = std::string("TYCHE_ZSTD_DICT: ") + path + (n == 0 ? " is empty" : " is longer than TYCHE_LZ4_DICT_MAX (" +
+                      std::to_string(TYCHE_LZ4_DICT_MAX) + " bytes)");
+        return;
+    }
+    tyche_lz4_dict *d = dict_create(buf.data(), (uint32_t)n);
+    if (d && zdict_structured(d)) {
+        dict_release(d);
+        S.env_error = std::string("TYCHE_ZSTD_DICT: ") + path + " begins with ZSTD_DICT_MAGIC (37 A4 30 EC), a structured "
+                      "dictionary; structured dictionaries are not supported, only raw content";
+        return;
+    }
+    S.d = d;
+}
+// The dictionary a zstd host call runs with (retained: the caller releases it), or NULL.
+// TYCHE_E_BAD_ARGS when the environment names a dictionary file that cannot serve.
+int zdict_for_host_call(const tyche_lz4_dict **out) {
+    ZDictSlot &S = zdict_slot();
+    std::lock_guard<std::mutex> g(S.mu);
+    zdict_env_locked(S);
+    *out = nullptr;
+    if (!S.env_error.empty()) {
+        t_error = S.env_error;
+        return TYCHE_E_BAD_ARGS;
+    }
+    if (S.d) {
+        dict_retain(S.d);
+        *out = S.d;
+    }
+    return TYCHE_E_OK;
 }
 
 // ---- training (lz4_dict_train.hip).  The rules that need no device come first, so that they read
@@ -1167,6 +1279,68 @@ int tyche_lz4_decompress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch
     return TYCHE_E_OK;
 }
 
+// ------------------------------------------------- zstd with the shared dictionary
+int tyche_zstd_compress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream) {
+    if (!d || !batch) return TYCHE_E_BAD_ARGS;
+    if (zdict_structured(d)) return zdict_structured_error();
+    if (batch->count == 0) return TYCHE_E_OK;
+    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
+    const uint32_t in_cap = encode_in_cap(*batch);
+    if ((uint64_t)in_cap + d->len > 65536u) return dict_reach_error("the launch's largest page", in_cap, d->len, "zstd");
+    DeviceGuard keep;
+    if (int rc = stream_device((hipStream_t)stream)) return rc;
+    Lz4DictDev img;
+    const void *seed = nullptr;
+    if (int rc = zdict_on_device(d, &img, &seed)) return rc;
+    hipError_t e = compress_launch_fails() ? hipErrorLaunchFailure   // the FAIL_COMPRESS_EVERY test hook, as launch_encode
+                                           : launch_zstd_encode_dict(*batch, in_cap, img, seed, false, (hipStream_t)stream);
+    if (e != hipSuccess) return fail("zstd dictionary encode launch", e);
+    return TYCHE_E_OK;
+}
+
+int tyche_zstd_decompress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream) {
+    if (!d || !batch) return TYCHE_E_BAD_ARGS;
+    if (zdict_structured(d)) return zdict_structured_error();
+    if (batch->count == 0) return TYCHE_E_OK;
+    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
+    const uint32_t out_cap = batch->dst_capacity;
+    if ((uint64_t)out_cap + d->len > 65536u) return dict_reach_error("the launch's largest capacity", out_cap, d->len, "zstd");
+    DeviceGuard keep;
+    if (int rc = stream_device((hipStream_t)stream)) return rc;
+    Lz4DictDev img;
+    if (int rc = dict_on_device(d, &img)) return rc;
+    // (a declared stream maximum is only a bound -- a slot width, say: above tyche_compress_bound of a
+    // 65,536-byte window it is taken as that, and a page whose stream is longer still gets INT32_MIN)
+    const uint32_t in_cap = std::min(decode_in_cap(*batch, zstd_bound(out_cap)), zstd_bound(65536u));
+    hipError_t e = launch_zstd_decode_dict(*batch, in_cap, out_cap, img, false, (hipStream_t)stream);
+    if (e != hipSuccess) return fail("zstd dictionary decode launch", e);
+    return TYCHE_E_OK;
+}
+
+int tyche_zstd_use_dict(const tyche_dict_t *d) {
+    if (d && zdict_structured(d)) return zdict_structured_error();
+    ZDictSlot &S = zdict_slot();
+    const tyche_lz4_dict *old;
+    {
+        std::lock_guard<std::mutex> g(S.mu);
+        S.env_done = true;   // an explicit choice replaces whatever TYCHE_ZSTD_DICT names
+        S.env_error.clear();
+        old = S.d;
+        if (d) dict_retain(d);
+        S.d = d;
+    }
+    dict_release(old);
+    return TYCHE_E_OK;
+}
+
+tyche_dict_t *tyche_zstd_current_dict(void) {
+    ZDictSlot &S = zdict_slot();
+    std::lock_guard<std::mutex> g(S.mu);
+    zdict_env_locked(S);
+    if (S.d) dict_retain(S.d);
+    return const_cast<tyche_lz4_dict *>(S.d);
+}
+
 // ----------------------------------------------------------- host batch API
 int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const void *const *src,
                         const uint32_t *src_lengths, void *const *dst, const uint32_t *dst_capacities,
@@ -1190,6 +1364,26 @@ int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const
         if (dict.d && knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
         if (!dict.d)
             if (int rc = auto_collect(n, src, src_lengths, &trained_from)) return rc;
+    }
+    // zstd with a process-wide dictionary: the same rule with the zstd slot's dictionary
+    if (compressor_id == TYCHE_ZSTD_COMPRESSOR_ID) {
+        if (int rc = zdict_for_host_call(&dict.d)) return rc;
+        if (const tyche_lz4_dict *d = dict.d) {
+            DictUploadNote note;
+            return note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
+                            [d, &note](const tyche_batch_t &b, hipStream_t s, bool) {
+                                Lz4DictDev img;
+                                const void *seed = nullptr;
+                                if (const hipError_t ue = note.upload(d, &img, &seed)) return ue;
+                                const uint32_t longest = std::max(b.max_src_length, 1u), reach = 65536u - d->len;
+                                if (longest <= reach)
+                                    return compress_launch_fails() ? hipErrorLaunchFailure
+                                                                   : launch_zstd_encode_dict(b, longest, img, seed, false, s);
+                                const hipError_t e = launch_encode(TYCHE_ZSTD_COMPRESSOR_ID, b, longest, s);
+                                if (e != hipSuccess) return e;
+                                return launch_zstd_encode_dict(b, reach, img, seed, true, s);
+                            }, false, direct));
+        }
     }
     if (trained_from.dict_len) {
         // compressed plain like every call before the install, then trained and installed
@@ -1230,11 +1424,28 @@ int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, c
                               [](const tyche_batch_t &b, hipStream_t s, bool) {
                                   return launch_zlib_inflate(b, b.dst_capacity, s);
                               }, true);
-    if (compressor_id == TYCHE_ZSTD_COMPRESSOR_ID)
-        return run_host(n, src, src_lengths, dst, dst_capacities, results,
-                              [](const tyche_batch_t &b, hipStream_t s, bool) {
-                                  return launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
-                              }, true);
+    if (compressor_id == TYCHE_ZSTD_COMPRESSOR_ID) {
+        // With a process-wide zstd dictionary the pages it reaches (capacity + dictionary <= 65536)
+        // take the dictionary decoder; a chunk that also holds larger capacities runs today's launch
+        // first, for them, and the dictionary launch then decodes the pages in reach over whatever
+        // that left.
+        DictHold zdict;
+        if (int rc = zdict_for_host_call(&zdict.d)) return rc;
+        const tyche_lz4_dict *zd = zdict.d;
+        DictUploadNote znote;
+        return znote.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
+                              [zd, &znote](const tyche_batch_t &b, hipStream_t s, bool) {
+                                  if (!zd) return launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
+                                  Lz4DictDev img;
+                                  if (const hipError_t ue = znote.upload(zd, &img)) return ue;
+                                  const uint32_t reach = 65536u - zd->len;
+                                  const uint32_t in_cap = std::min(b.max_src_length, zstd_bound(65536u));
+                                  if (b.dst_capacity <= reach) return launch_zstd_decode_dict(b, in_cap, b.dst_capacity, img, false, s);
+                                  const hipError_t e = launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
+                                  if (e != hipSuccess) return e;
+                                  return launch_zstd_decode_dict(b, in_cap, reach, img, true, s);
+                              }, true));
+    }
     // A capacity above TYCHE_LZ4_MAX_PAGE is refused by the launch of the chunk that holds it, as
     // every capacity beyond the decoders' LDS used to be: TYCHE_E_DEVICE, earlier chunks drained.
     // So is, at the chunk that holds its first large page, a bulk batch that mixes classes: one that

@@ -849,12 +849,27 @@ __device__ __forceinline__ void wave_match(uint8_t *out, int32_t d, int32_t off,
     }
 }
 
+// How far below window position 0 a match may begin.  The plain decoders: nowhere (an empty
+// type, so their instantiations carry no field for it).  kDict (zstd_decode_dict_kernel): the
+// dictionary's D bytes stand in LDS right in front of the window, out[-D, 0), and an offset may
+// reach position + D -- ZSTD_decompress_usingDict's rule for a raw-content dictionary
+// (zstd_decompress.c:831, the vBase check).
+template <bool kDict>
+struct DictReach {
+    int32_t d;
+};
+template <>
+struct DictReach<false> {
+    static constexpr int32_t d = 0;
+};
+
 // Applies n <= 64 decoded sequences (lane j: ll, ml, off) in order.  op: output
 // position (frame offset); lp: literal cursor (literal k lives at lit[k]).
 // Returns false on a reference exec error.
+template <bool kDict = false>
 __device__ bool exec_batch(uint8_t *out, const uint8_t *lit, bool lit_in_window, int32_t lit_win_base, uint32_t n,
                            uint32_t ll, uint32_t ml, uint32_t off, int32_t &op, int32_t &lp, int32_t lsize,
-                           int32_t cap, uint32_t lane) {
+                           int32_t cap, uint32_t lane, DictReach<kDict> reach = {}) {
     const bool act = lane < n;
     const int32_t olen = act ? (int32_t)(ll + ml) : 0;
     const int32_t llen = act ? (int32_t)ll : 0;
@@ -863,7 +878,7 @@ __device__ bool exec_batch(uint8_t *out, const uint8_t *lit, bool lit_in_window,
     const int32_t l0 = lp + li - llen;    // its first literal
     const int32_t d = o + (int32_t)ll;    // match destination
     // ZSTD_execSequence checks (zstd_decompress.c:940-954)
-    const bool bad = act && (o + olen > cap || l0 + llen > lsize || (int32_t)off > d);
+    const bool bad = act && (o + olen > cap || l0 + llen > lsize || (int32_t)off > d + reach.d);
     if (__ballot(bad)) return false;
     const int32_t out_end = op + (int32_t)rdlane((uint32_t)oi, kWave - 1);
     const int32_t lit_end = lp + (int32_t)rdlane((uint32_t)li, kWave - 1);
@@ -1151,9 +1166,10 @@ __device__ bool publish_table(const Ent &E, SeqTables &T, const uint32_t *cells,
 // One compressed block at in[ip, ip+n); output from op (frame offset) up to cap.
 // Returns bytes written or < 0.  kSplit: pass 1 (entries and literals to E;
 // ecur / litc are the page's entry and literal cursors).
-template <bool kSplit>
+template <bool kSplit, bool kDict = false>
 __device__ int32_t decode_block(const Work &W, SeqTables &T, const Ent &E, uint32_t &ecur, uint32_t &litc,
-                                int32_t ip, int32_t n, int32_t op, int32_t cap, uint32_t lane) {
+                                int32_t ip, int32_t n, int32_t op, int32_t cap, uint32_t lane,
+                                DictReach<kDict> reach = {}) {
     const uint8_t *in = W.in;
     SPROF_DECL
     ip = ru(ip);
@@ -1436,7 +1452,8 @@ __device__ int32_t decode_block(const Work &W, SeqTables &T, const Ent &E, uint3
                 op += (int32_t)rdlane((uint32_t)wave_incl_sum(lane < k ? (int32_t)(vll + vml) : 0), kWave - 1);
                 lp += (int32_t)rdlane((uint32_t)wave_incl_sum(lane < k ? (int32_t)vll : 0), kWave - 1);
 #else
-                if (!exec_batch(W.win, lit, lit_in_window, lit_win_base, k, vll, vml, voff, op, lp, lsize, cap, lane))
+                if (!exec_batch<kDict>(W.win, lit, lit_in_window, lit_win_base, k, vll, vml, voff, op, lp, lsize, cap, lane,
+                                       reach))
                     return kErr;
 #endif
             }
@@ -1470,8 +1487,13 @@ __device__ int32_t decode_block(const Work &W, SeqTables &T, const Ent &E, uint3
 // ZSTD_decompressFrame (zstd_decompress.c:1369-1436) for the frame staged at
 // W.in[0, L).  Returns the decoded size or < 0.
 // kSplit: pass 1 -- returns 0 or < 0 and leaves the page's entries in E.
-template <bool kSplit>
-__device__ int32_t decode_frame(const Work &W, const Ent &E, int32_t L, int32_t cap, uint32_t lane, bool jobs = false) {
+// kDict (one-wave decode only): matches may begin up to reach.d bytes in front of the window
+// (DictReach).  The frame is an ordinary one -- no dictionary ID, repeat offsets {1, 4, 8} -- and
+// everything but the offset check is the plain decode.
+template <bool kSplit, bool kDict = false>
+__device__ int32_t decode_frame(const Work &W, const Ent &E, int32_t L, int32_t cap, uint32_t lane, bool jobs = false,
+                                DictReach<kDict> reach = {}) {
+    static_assert(!(kSplit && kDict), "the split decode has no dictionary variant");
     const uint8_t *in = W.in;
     if (L < 9) return kErr;
     stage_range(W, 0, 18, lane);   // the frame header (<= 18 bytes)
@@ -1538,7 +1560,7 @@ __device__ int32_t decode_frame(const Work &W, const Ent &E, int32_t L, int32_t 
         if (csize > remaining) return kErr;
         int32_t dec;
         if (btype == 2u) {
-            dec = decode_block<kSplit>(W, T, E, ecur, litc, ip, csize, op, cap, lane);
+            dec = decode_block<kSplit, kDict>(W, T, E, ecur, litc, ip, csize, op, cap, lane, reach);
         } else if (btype == 0u) {
             if (csize > cap - op) return kErrDst;
             if constexpr (kSplit) {
@@ -1674,6 +1696,65 @@ __global__ __launch_bounds__(64) void zstd_decode_kernel(tyche_batch_t b, size_t
         return;
     }
     for (size_t j = blockIdx.x; j < count; j = ctr ? claim_page(ctr, lane) : j + gridDim.x) do_page(j);   // engine.h
+}
+
+// The one-wave decode with a shared raw-content dictionary (tyche_zstd_decompress_batch_dict, and
+// the host entry points once a process-wide zstd dictionary is installed): results[i] and the
+// bytes are those of ZSTD_decompress_usingDict(dst, capacity, frame, n, dict, D).  LDS holds
+//     [ dictionary (dpad) | window | frame | tables ]
+// -- zstd_decode_kernel's layout behind the handle's decoder image, whose D bytes end where the
+// window starts, so a match that begins in the dictionary (and may run over the seam) is the copy
+// it is anywhere else.  The dictionary is staged once per workgroup: the decoder only reads it.
+// per_page: the host entry points' reach rule -- a page with dst_cap + D > 65536 is not this
+// kernel's (its result is left alone: the plain launch over the same batch owns it).
+__global__ __launch_bounds__(64) void zstd_decode_dict_kernel(tyche_batch_t b, uint32_t in_cap, uint32_t out_cap,
+                                                              Layout lay, Lz4DictDev d, uint32_t per_page,
+                                                              unsigned *ctr) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t lane = threadIdx.x;
+    uint8_t *base = smem + d.dpad;   // the window; the dictionary ends here
+    {
+        const u32x4 *g = (const u32x4 *)d.dec;   // dpad bytes, the dictionary right-aligned in them
+        u32x4 *l = (u32x4 *)smem;
+        for (uint32_t v = lane; v < (d.dpad >> 4); v += kWave) l[v] = g[v];
+    }
+    Work W;
+    W.gsrc = nullptr;
+    W.ghead = 0;
+    W.gL = 0;
+    W.wlo = W.whi = 0;
+    W.win = base;
+    W.huf = (uint16_t *)(base + lay.off_huf);
+    W.hpair = base + lay.off_hp;
+    W.ll = (uint32_t *)(base + lay.off_ll);
+    W.of = (uint32_t *)(base + lay.off_of);
+    W.ml = (uint32_t *)(base + lay.off_ml);
+    W.wt = (uint32_t *)(base + lay.off_wt);
+    W.norm = (int16_t *)(base + lay.off_norm);
+    W.next = (uint16_t *)(base + lay.off_next);
+    W.w = base + lay.off_w;
+    uint8_t *stage = base + lay.off_in;
+    const DictReach<true> reach{(int32_t)d.dlen};
+    for (size_t page = blockIdx.x; page < b.count; page = ctr ? claim_page(ctr, lane) : page + gridDim.x) {
+        const PageRef p = batch_page(b, page);
+        if (per_page && (uint64_t)p.dst_cap + d.dlen > 65536u) continue;
+        int32_t rv;
+        if (p.src_len > in_cap || p.dst_cap > out_cap) {
+            rv = kResultTooLarge;
+        } else {
+            WAVE_SYNC();
+            const uint32_t head = stage_in(p.src, p.src_len, stage, lane, kWave);
+            uint8_t *in = stage + head;
+            WAVE_SYNC();
+            if (lane < kStreamPad / 4) lds_st32(in + p.src_len + lane * 4, 0u);
+            WAVE_SYNC();
+            W.in = in;
+            rv = decode_frame<false, true>(W, Ent{}, (int32_t)p.src_len, (int32_t)p.dst_cap, lane, false, reach);
+            WAVE_SYNC();
+            if (rv > 0) stage_out(p.dst, W.win, (uint32_t)rv, lane, kWave);
+        }
+        if (lane == 0) b.results[page] = rv;
+    }
 }
 
 // ---- sequence jobs: one page per lane
@@ -2693,6 +2774,25 @@ hipError_t launch_zstd_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t 
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// One kernel for every batch size (zstd_decode_dict_kernel): the split decode has no dictionary
+// variant.  per_page: pages beyond the reach are skipped; else out_cap + D must not exceed 65,536.
+// LDS: dpad + the one-wave layout; with in_cap held to the longest frame a 65,536-byte window's
+// page can need (the caller's clamp) at most 139.9 KiB.
+hipError_t launch_zstd_decode_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &d,
+                                   bool per_page, hipStream_t s) {
+    if (b.count == 0) return hipSuccess;
+    if ((uint64_t)out_cap + d.dlen > 65536u || d.dpad < d.dlen || (d.dpad & 15u)) return hipErrorInvalidValue;
+    const Layout lay = make_layout(in_cap, out_cap);
+    const size_t lds = (size_t)d.dpad + lay.total;
+    if (lds > 160u * 1024u) return hipErrorInvalidValue;
+    const size_t grid = page_grid((const void *)zstd_decode_dict_kernel, kWave, lds, b.count);
+    WorkCounter ctr(s, grid < b.count);
+    if (!ctr.get()) return hipErrorOutOfMemory;
+    hipLaunchKernelGGL(zstd_decode_dict_kernel, dim3((unsigned)grid), dim3(kWave), lds, s, b, in_cap, out_cap, lay, d,
+                       per_page ? 1u : 0u, ctr.get());
+    return hipGetLastError();
 }
 
 }  // namespace tyche

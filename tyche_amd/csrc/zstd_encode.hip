@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <vector>
 
 #include "engine.h"
 #include "lds_io.h"
@@ -450,7 +451,10 @@ constexpr uint32_t kHufMaxBits = 11;     // HUF_TABLELOG_DEFAULT
 // the tail of the output buffer as scratch while an LDS histogram is built;
 // after the code is chosen the streams are written at o, below the scratch.
 // Returns the section size, or 0 when raw literals are to be used instead.
-__device__ uint32_t huf_literals(Enc &e, uint32_t n, uint32_t trail, uint32_t lit_total, uint32_t o, uint32_t lane) {
+// (forced inline: every kernel had it inlined while four call sites existed; with the dictionary
+// encode's fifth the inliner stopped, and the one-kernel encode went from 206 VGPRs and no scratch
+// to 226 and 220 bytes of scratch around the call)
+__device__ __forceinline__ uint32_t huf_literals(Enc &e, uint32_t n, uint32_t trail, uint32_t lit_total, uint32_t o, uint32_t lane) {
     const uint32_t lh = 3u + (lit_total >= 1024u) + (lit_total >= 16384u);
     const bool single = lit_total < 256u;
     if (e.cap < lit_total || e.cap - lit_total < o + lh + 272u) return 0;   // room for header + weights below the scratch
@@ -604,6 +608,11 @@ __device__ uint32_t huf_literals(Enc &e, uint32_t n, uint32_t trail, uint32_t li
 
 // Writes one block covering page bytes [s.bstart, bend) with the buffered
 // sequences; `last` sets Last_Block.  Returns false if it does not fit.
+// kDict (the dictionary encode's pass A2): the compressed size's bound counts the three NCount
+// headers only for the blocks that write them (64 sequences and more).  A short page that one
+// match into the dictionary covers is a block of one sequence, and the plain bound would store it
+// raw.  The plain encoders keep their bound: it decides their bytes.
+template <bool kDict = false>
 __device__ __forceinline__ bool emit_block(Enc &e, uint32_t bend, bool last, uint32_t lane) {
     SPROF_DECL
     const uint32_t n = e.nseq, blen = bend - e.bstart;
@@ -634,7 +643,7 @@ __device__ __forceinline__ bool emit_block(Enc &e, uint32_t bend, bool last, uin
     const uint32_t nsh = n < 0x7Fu ? 1u : (n < 0x7F00u ? 2u : 3u);
     // upper bound of the FSE bitstream: every state emits at most its table log
     const uint32_t fse_bound = n ? (n * kStateBits + xbits + kStateBits + 8u + 7u) / 8u + 1u : 0u;
-    const uint32_t comp_bound = fl + lit_total + nsh + (n ? 1u + 3u * 48u : 0u) + fse_bound;   // + NCount headers
+    const uint32_t comp_bound = fl + lit_total + nsh + (n ? 1u + (kDict && n < 64u ? 0u : 3u * 48u) : 0u) + fse_bound;   // + NCount headers
     const uint32_t hdr = e.op;                              // block header position
     if (comp_bound >= blen) {
         // ---- raw block (Block_Type 0): header + the page bytes
@@ -903,21 +912,24 @@ static_assert(kZBlk >= kWave && (65536u / 4u + kZBlk - 1u) / kZBlk + 1u <= kMaxB
 // 0 when a bound is exceeded (the page is then stored uncompressed by the caller).
 // parse(sink) runs the parse over the page and returns its last anchor.  The literals go
 // to the area's literal region as the sequences come (copy_runs from the page `in`).
+// base (dictionary parse, zstd_parse_dict_kernel): `in` is a window whose first `base` bytes are
+// the dictionary and L its end; the parse starts at base, positions are window positions, and the
+// parse blocks' bounds go to the area as page positions, which is what pass A2 reads.
 template <typename Parse>
 __device__ __forceinline__ int32_t parse_to_area_with(const uint8_t *in, uint32_t L, uint8_t *area, uint32_t rec_cap,
                                                       uint32_t lane, Parse &&parse, const uint8_t *sink_in,
-                                                      uint32_t *map) {
+                                                      uint32_t *map, uint32_t base = 0) {
     uint2 *S = (uint2 *)area_rec(area);   // one part: the sequence map below is the identity
     uint8_t *lits = area_lit(area, rec_cap);
-    uint32_t nseq = 0, bseq = 0, bstart = 0, cursor = 0, npb = 0;
+    uint32_t nseq = 0, bseq = 0, bstart = base, cursor = base, npb = 0;
     uint32_t a_lit = 0, a_span = 0, a_xb = 0;   // this lane's share of the block's sums
     uint32_t lpos = 0, blit = 0;                // literals copied; the block's first
     auto put_pblk = [&](uint32_t bend) {
         const uint32_t lit = huf::wave_sum(a_lit), span = huf::wave_sum(a_span), xb = huf::wave_sum(a_xb);
         if (lane == 0) {
             uint32_t *P = area_pblk(area, npb);
-            P[0] = bstart;
-            P[1] = bend;
+            P[0] = bstart - base;
+            P[1] = bend - base;
             P[2] = bseq;
             P[3] = nseq - bseq;
             P[4] = lit;
@@ -976,6 +988,7 @@ __device__ __forceinline__ int32_t parse_to_area(const uint8_t *in, uint32_t L, 
 
 // Pass A2: frame header and every block of the page from the area (the page
 // itself is read from global memory).  Returns the gapped frame size or 0.
+template <bool kDict = false>
 __device__ __forceinline__ int32_t emit_page(const uint8_t *src, uint32_t L, uint8_t *area, uint32_t rec_cap,
                                              uint8_t *map, uint2 *stage, uint32_t *htab, uint8_t *wts, uint8_t *dst,
                                              uint32_t cap, uint32_t logcap, uint32_t lane) {
@@ -1025,7 +1038,7 @@ __device__ __forceinline__ int32_t emit_page(const uint8_t *src, uint32_t L, uin
         e.nseq = __builtin_amdgcn_readfirstlane(P[3]);
         e.psum = P + 4;
         e.lofs = __builtin_amdgcn_readfirstlane(P[7]);
-        if (!emit_block(e, bend, k + 1u == npb, lane)) return 0;
+        if (!emit_block<kDict>(e, bend, k + 1u == npb, lane)) return 0;
     }
     if (lane == 0) ((uint32_t *)area)[0] = e.nblk;
     return (int32_t)e.op;
@@ -1084,6 +1097,75 @@ __global__ __launch_bounds__(64) void zstd_encode_kernel(tyche_batch_t b, size_t
         p = pn;
         head = nhead;
         TYCHE_NEXT_PAGE_INSTALL(kPrefetchVec, kWave, p.src, p.src_len, in_cap, stage, lane)
+    }
+}
+
+// ---- pass A1 with a shared dictionary (tyche_zstd_compress_batch_dict, and the host entry points
+// once a process-wide zstd dictionary is installed).
+//
+// A raw-content dictionary of D bytes followed by a page of L bytes is one window (L + D <=
+// 65536: positions and the sequence records' offsets stay 16 bits): the frame is an ordinary one
+// whose offsets may reach back into the dictionary, what ZSTD_decompress_usingDict restores.  One
+// wave per page stages  [ table | records | copy map | dictionary tail | page ]  in LDS, as
+// lz4_encode_dict_kernel does: the dictionary's last D' = D & ~63 bytes stand right before the
+// page's first byte (the handle's image holds them at all 16 byte shifts a page's first vector
+// can have), window position p is LDS byte p, and parse_page runs from start = D' exactly as a
+// part of the split parse runs from its start with the positions before it in the table.  Those
+// positions are not hashed per page: the table starts as a copy of the handle's seeded table
+// (zstd_dict_seed_table below, 7,424 bytes, built once per handle on the host).  The parse's
+// sequences, literals and parse blocks go to the page's area as pass A1 always leaves them (block
+// bounds as page positions); passes A2, B and C never see a position, only lengths and offsets,
+// so they take offsets above the page position as they are -- sequence records hold 16-bit
+// offsets and 17-bit offset codes whatever the position.
+// per_page: the host entry points' reach rule -- a page with src_len + D > 65536 is not this
+// launch's (status kStSkip: passes A2 and B pass it by and pass C leaves its result alone).
+//
+// LDS: 7,424 + 512 + 256 + D' + the page's vectors + 64: 28.2 KiB at D = 4 KiB and 16 KiB pages
+// (5 per CU), 72.2 KiB at the window's limit (2 per CU).
+constexpr int32_t kStSkip = INT32_MIN + 1;   // pass A1's status of a page the launch does not own (negative: A2 and B pass it by)
+constexpr size_t kDictFront = kTableSlots * sizeof(uint16_t) + kWave * 8 + kWave * 4;   // table, 64 records, copy map
+__global__ __launch_bounds__(64) void zstd_parse_dict_kernel(tyche_batch_t b, size_t first, size_t count, uint32_t in_cap,
+                                                             Lz4DictDev d, const uint32_t *seed, uint32_t per_page,
+                                                             unsigned *ctr, uint8_t *ws, size_t ws_page, int32_t *st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t lane = threadIdx.x;
+    uint16_t *table = (uint16_t *)smem;
+    uint2 *rec = (uint2 *)(smem + kTableSlots * sizeof(uint16_t));
+    uint32_t *lmap = (uint32_t *)(rec + kWave);
+    uint8_t *dstage = smem + kDictFront;   // the dictionary tail's vectors
+    const uint32_t DE = d.enc_len;         // a multiple of 64
+    uint8_t *stage = dstage + DE;          // the page's vectors
+    for (size_t page = blockIdx.x; page < count; page = ctr ? claim_page(ctr, lane) : page + gridDim.x) {
+        const PageRef p = batch_page(b, first + page);
+        int32_t rv;
+        if (per_page && (uint64_t)p.src_len + d.dlen > 65536u) {
+            rv = kStSkip;
+        } else if (p.src_len > in_cap) {
+            rv = kResultTooLarge;
+        } else {
+            WAVE_SYNC();
+            // the page first: its first vector also holds up to 15 bytes in front of the page, which
+            // the dictionary's last bytes then replace
+            const uint32_t head = stage_in(p.src, p.src_len, stage, lane, kWave);
+            {
+                const u32x4 *g = (const u32x4 *)(d.enc + (size_t)head * d.enc_stride);
+                u32x4 *l = (u32x4 *)dstage;
+                for (uint32_t v = lane; v < (DE >> 4); v += kWave) l[v] = g[v];
+                if (DE && lane < head) stage[lane] = d.enc[(size_t)head * d.enc_stride + DE + lane];
+                const u32x4 *gt = (const u32x4 *)seed;
+                for (uint32_t w = lane; w < kTableSlots / 8; w += kWave) ((u32x4 *)table)[w] = gt[w];
+            }
+            WAVE_SYNC();
+            uint8_t *in = dstage + head;         // window position 0
+            const uint32_t W = DE + p.src_len;   // the window's end
+            in[W + lane] = 0;                    // the parse's zero pad
+            WAVE_SYNC();
+            rv = parse_to_area_with(
+                in, W, ws + page * ws_page, enc_rec_cap(in_cap), lane,
+                [&](auto &sink) { return lzp::parse_page<true, false, kZWays>(in, W, table, rec, lane, sink, DE); },
+                TYCHE_SINK_BACK ? in : nullptr, lmap, DE);
+        }
+        if (lane == 0) st[page] = rv;
     }
 }
 
@@ -1446,6 +1528,7 @@ __global__ __launch_bounds__(kNW * 64) void zstd_parse_split_kernel(tyche_batch_
 
 // ---- pass A2
 constexpr uint32_t kA2Lds = kWave + kWave * 8u + kHtab * 4u + 256u;   // map, stage, htab, weights
+template <bool kDict = false>   // kDict: the area was written by zstd_parse_dict_kernel (emit_block's bound)
 __global__ __launch_bounds__(64) void zstd_block_kernel(tyche_batch_t b, size_t first, size_t count, uint32_t in_cap,
                                                         uint8_t *ws, size_t ws_page, int32_t *st, unsigned *ctr,
                                                         uint32_t logcap) {
@@ -1460,7 +1543,7 @@ __global__ __launch_bounds__(64) void zstd_block_kernel(tyche_batch_t b, size_t 
         if (s0 != 1) continue;   // 0: does not fit; kResultTooLarge passes through
         const PageRef p = batch_page(b, first + j);
         WAVE_SYNC();
-        const int32_t rv = emit_page(p.src, p.src_len, ws + j * ws_page, enc_rec_cap(in_cap), map, stage, htab, wts,
+        const int32_t rv = emit_page<kDict>(p.src, p.src_len, ws + j * ws_page, enc_rec_cap(in_cap), map, stage, htab, wts,
                                      p.dst, p.dst_cap, logcap, lane);
         if (lane == 0) st[j] = rv;
     }
@@ -1671,6 +1754,9 @@ __device__ __forceinline__ int32_t pack_page_wave(uint8_t *dst, const uint8_t *a
     }
     return (int32_t)q;
 }
+// kSkip (the dictionary encode behind a host call): a page with status kStSkip is another launch's
+// (beyond the dictionary's reach); its result is left alone.
+template <bool kSkip = false>
 __global__ __launch_bounds__(64) void zstd_pack_kernel(tyche_batch_t b, size_t first, size_t count, uint8_t *ws,
                                                        size_t ws_page, const int32_t *st) {
     const uint32_t lane = threadIdx.x;
@@ -1701,7 +1787,7 @@ __global__ __launch_bounds__(64) void zstd_pack_kernel(tyche_batch_t b, size_t f
         }
         rv = (int32_t)q;
     }
-    if (j < count && !wave_page) b.results[first + j] = rv;
+    if (j < count && !wave_page && !(kSkip && rv == kStSkip)) b.results[first + j] = rv;
     for (uint64_t m = __ballot(wave_page); m; m &= m - 1ull) {
         const uint32_t k = (uint32_t)__builtin_ctzll(m);
         const size_t jj = (size_t)blockIdx.x * kWave + k;
@@ -1766,10 +1852,10 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
     const bool four = kZWays == 2 && (long)in_cap <= knob("ZSTD_WAYS4_MAX", 16384);
     const void *k1 = four ? (const void *)zstd_encode_kernel<true, 4> : (const void *)zstd_encode_kernel<true>;
     const size_t ncu = prepare_launch(k1);
-    (void)prepare_launch((const void *)zstd_block_kernel);
+    (void)prepare_launch((const void *)zstd_block_kernel<false>);
     (void)prepare_launch((const void *)zstd_fse_kernel);
-    (void)prepare_launch((const void *)zstd_pack_kernel);
-    const size_t cu1 = blocks_per_cu(k1, 64, lds1), cu2 = blocks_per_cu((const void *)zstd_block_kernel, 64, kA2Lds);
+    (void)prepare_launch((const void *)zstd_pack_kernel<false>);
+    const size_t cu1 = blocks_per_cu(k1, 64, lds1), cu2 = blocks_per_cu((const void *)zstd_block_kernel<false>, 64, kA2Lds);
     // pass A1 on 1 to 4 waves per page (1: the one-wave parse, 4-way buckets, up to 16 KiB):
     // 4 by default above 16 KiB.  Round 3, 32 KiB bench pages with one block per page
     // (profiles/r03_zstd_parse_ab.log): 2 parts 793 ms per 1M pages at ratio 4.940; 3 parts 823
@@ -1838,13 +1924,98 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
             const size_t g = std::min<size_t>(n, ncu * cu2);
             WorkCounter ctr(s, g < n);
             if (!ctr.get()) return hipErrorOutOfMemory;
-            hipLaunchKernelGGL(zstd_block_kernel, dim3((unsigned)g), dim3(kWave), kA2Lds, s, b, first, n, in_cap, ws,
+            hipLaunchKernelGGL(zstd_block_kernel<false>, dim3((unsigned)g), dim3(kWave), kA2Lds, s, b, first, n, in_cap, ws,
                                page_bytes, st, ctr.get(), logcap);
         }
         hipLaunchKernelGGL(zstd_fse_kernel, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave),
                            kWave * kFseSlot.words * 4u, s, b, first, n, ws, page_bytes, (const int32_t *)st);
-        hipLaunchKernelGGL(zstd_pack_kernel, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, s, b, first, n, ws,
+        hipLaunchKernelGGL(zstd_pack_kernel<false>, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, s, b, first, n, ws,
                            page_bytes, (const int32_t *)st);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// The dictionary parse's table as a page finds it (zstd_parse_dict_kernel): kZWays = 2 positions
+// per bucket of the dictionary tail's n = D & ~63 bytes, keyed as parse_page keys its own inserts
+// (bucket_of<2> of TYCHE_HASH_BYTES = 5 bytes), for every position whose five bytes lie inside the
+// tail.  Way 0 (tried first) is the bucket's latest position, as the parse would leave it; way 1
+// its earliest instead of its second latest: a long dictionary puts 8 to 17 positions into a
+// bucket, and with the two latest kept, nothing in its first three quarters could ever be found.
+// An empty way is position 0, as in a zeroed table (a candidate is verified by its bytes).
+size_t zstd_dict_seed_bytes() { return kTableSlots * sizeof(uint16_t); }
+void zstd_dict_seed_table(const uint8_t *tail, uint32_t n, void *table_out) {
+    static_assert(kZWays == 2 && TYCHE_HASH_BYTES == 5, "the seeded table is hashed for parse_page<true, false, 2>");
+    constexpr uint32_t nb = kTableSlots / 2u;
+    uint32_t *T = (uint32_t *)table_out;
+    std::fill(T, T + nb, 0u);
+    std::vector<uint8_t> used(nb, 0);
+    for (uint32_t j = 0; j + 5u <= n; j++) {
+        uint64_t x = 0;
+        for (uint32_t k = 0; k < 5u; k++) x |= (uint64_t)tail[j + k] << (8u * k);
+        const uint64_t hx = x * 0xCF1BBCDCB7A56463ull;
+        const uint32_t h = (uint32_t)(((hx >> 32) * (uint64_t)nb) >> 32);
+        if (!used[h]) {
+            used[h] = 1;
+            T[h] = j | (j << 16);   // the bucket's earliest position in both ways
+        } else {
+            T[h] = j | (T[h] & 0xFFFF0000u);
+        }
+    }
+}
+
+// The four-pass encode with the dictionary parse as pass A1, for every batch size: a page's bytes
+// depend on the page and the dictionary alone.  seed: the handle's seeded table on this device.
+// per_page: pages beyond the reach are skipped; else in_cap + D must not exceed 65,536.
+hipError_t launch_zstd_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, const void *seed,
+                                   bool per_page, hipStream_t s) {
+    if (b.count == 0) return hipSuccess;
+    if ((uint64_t)in_cap + d.dlen > 65536u || in_cap > 65535u || d.enc_len > d.dlen || (d.enc_len & 63u) || !seed)
+        return hipErrorInvalidValue;
+    const size_t page_lds = (in_cap + 16u + kPad + 15u) & ~15u;
+    const size_t lds1 = kDictFront + d.enc_len + page_lds;
+    const uint32_t logcap = knob("ZSTD_FSE_LOG", 7) <= 6 ? 6u : 7u;
+    const size_t page_bytes = enc_area_bytes(in_cap);
+    size_t budget = (size_t)16 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (b.count * page_bytes > ((size_t)1 << 30) && hipMemGetInfo(&free_b, &total_b) == hipSuccess && ((free_b += scratch_idle_bytes()), true) &&
+        free_b / 4 < budget)
+        budget = free_b / 4;
+    const long mb = knob("ZSTD_SCRATCH_MB", 0);
+    if (mb > 0) budget = (size_t)mb << 20;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(b.count, budget / page_bytes));
+    const size_t st_bytes = (chunk * 4u + 255u) & ~(size_t)255u;
+    ScratchLease lease(s, st_bytes + chunk * page_bytes);
+    if (!lease.get()) return hipErrorOutOfMemory;
+    int32_t *st = (int32_t *)lease.get();
+    uint8_t *ws = (uint8_t *)lease.get() + st_bytes;
+    const void *k1 = (const void *)zstd_parse_dict_kernel;
+    const void *k2 = (const void *)zstd_block_kernel<true>;
+    const size_t ncu = prepare_launch(k1);
+    (void)prepare_launch(k2);
+    (void)prepare_launch((const void *)zstd_fse_kernel);
+    const size_t cu1 = blocks_per_cu(k1, 64, lds1), cu2 = blocks_per_cu(k2, 64, kA2Lds);
+    for (size_t first = 0; first < b.count; first += chunk) {
+        const size_t n = std::min(chunk, b.count - first);
+        {
+            const size_t g = std::min<size_t>(n, ncu * cu1);
+            WorkCounter ctr(s, g < n);
+            if (!ctr.get()) return hipErrorOutOfMemory;
+            hipLaunchKernelGGL(zstd_parse_dict_kernel, dim3((unsigned)g), dim3(kWave), lds1, s, b, first, n, in_cap, d,
+                               (const uint32_t *)seed, per_page ? 1u : 0u, ctr.get(), ws, page_bytes, st);
+        }
+        {
+            const size_t g = std::min<size_t>(n, ncu * cu2);
+            WorkCounter ctr(s, g < n);
+            if (!ctr.get()) return hipErrorOutOfMemory;
+            hipLaunchKernelGGL(zstd_block_kernel<true>, dim3((unsigned)g), dim3(kWave), kA2Lds, s, b, first, n, in_cap, ws,
+                               page_bytes, st, ctr.get(), logcap);
+        }
+        hipLaunchKernelGGL(zstd_fse_kernel, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave),
+                           kWave * kFseSlot.words * 4u, s, b, first, n, ws, page_bytes, (const int32_t *)st);
+        hipLaunchKernelGGL(zstd_pack_kernel<true>, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, s, b, first, n,
+                           ws, page_bytes, (const int32_t *)st);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
