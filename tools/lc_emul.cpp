@@ -9,11 +9,13 @@
 //
 //   g++ -O2 -shared -fPIC -o tools/bin/liblcemul.so tools/lc_emul.cpp
 //   int lc_emul_decode(const uint8_t *in, int L, uint8_t *out, int C, int R);
+//   long lc_emul_chunks(const uint8_t *in, int L, int C, int R);   the page's chunks: its lane's loop iterations
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <vector>
 
 typedef unsigned __int128 u128;
 using std::min;
@@ -95,7 +97,8 @@ static bool g_lut_ready = [] {
 }();
 
 template <int32_t R>
-static int lc_decode(const uint8_t *in, int32_t L, uint8_t *out, int32_t C) {
+static int lc_decode(const uint8_t *in, int32_t L, uint8_t *out, int32_t C, long *chunks = nullptr) {
+    if (chunks) *chunks = 0;
     if (C == 0) return (L == 1 && in[0] == 0) ? 0 : -1;
     if (L <= 0) return -1;
     alignas(16) uint8_t ring[R];
@@ -111,6 +114,7 @@ static int lc_decode(const uint8_t *in, int32_t L, uint8_t *out, int32_t C) {
     P.C = C;
     wfill(w16, in, L, 0);
     for (long chunk = 0; chunk < 100000000; chunk++) {
+        if (chunks) *chunks = chunk + 1;
         const int32_t op0 = P.op;
         int32_t st = kLParse, rv = 0, nrec = 0;
         uint32_t rec[kLC + 1];
@@ -194,4 +198,19 @@ extern "C" int lc_emul_decode(const uint8_t *in, int L, uint8_t *out, int C, int
            : R == 192 ? lc_decode<192>(in, L, out, C)
            : R == 160 ? lc_decode<160>(in, L, out, C)
                       : lc_decode<128>(in, L, out, C);
+}
+
+// the chunks the decoder takes for the page (0 for a page answered without decoding): what a lane of
+// the kernel spends on it in wave-loop iterations (tests/test_page_order_emul.py, the balance model)
+extern "C" long lc_emul_chunks(const uint8_t *in, int L, int C, int R) {
+    std::vector<uint8_t> out((size_t)(C > 0 ? C : 0) + 64);
+    long n = 0;
+#if LC_LINE == 64
+    if (R == 128) R = 192;
+#endif
+    (void)(R == 256   ? lc_decode<256>(in, L, out.data(), C, &n)
+           : R == 192 ? lc_decode<192>(in, L, out.data(), C, &n)
+           : R == 160 ? lc_decode<160>(in, L, out.data(), C, &n)
+                      : lc_decode<128>(in, L, out.data(), C, &n));
+    return n;
 }

@@ -2,6 +2,8 @@
 
     python -c "from tyche_amd import _build; _build.build(profile=True)"
     TYCHE_CODEC_LIB=tyche_amd/libtyche_codec_prof.so TYCHE_LZ4_LC=1 python tools/lc_profile.py
+TYCHE_LZ4_LC_ORDER=0 / 1 (and TYCHE_LZ4_LC_ORDER_WINDOW) select the page walk; the wave loop's iterations
+per wave are printed for it.
 Shares only (the stamps serialize the kernel a little); never quote its run time.
 """
 import ctypes
@@ -40,6 +42,14 @@ def main():
     print(f"pages {n}  wave-chunks {v[0]} ({v[0] * 64 / n:.0f} per page-lane)  general slot taken in "
           f"{100.0 * v[12] / chunks:.1f} % of chunks  pieces flushed per chunk {v[13] / chunks:.1f}  page ends per chunk "
           f"{v[14] / chunks:.2f}")
+    # the loop iterations of every wave (a wave runs until its slowest lane is done): the walk's balance
+    waves = min(4096, (n + 63) // 64)
+    per_wave = (ctypes.c_uint * waves)()
+    if lib.tyche_debug_lc_wave_iters(per_wave, waves) == 0:
+        it = [x for x in per_wave if x]
+        print(f"  walk: TYCHE_LZ4_LC_ORDER={os.environ.get('TYCHE_LZ4_LC_ORDER', 'default')} "
+              f"window {os.environ.get('TYCHE_LZ4_LC_ORDER_WINDOW', 'default')}: {len(it)} waves, iterations per wave "
+              f"mean {sum(it) / max(len(it), 1):.1f}  min {min(it)}  max {max(it)}  total {sum(it)}")
     for k, name in NAMES.items():
         print(f"  {name:20s} {100.0 * v[k] / max(tot, 1):5.1f} %   {v[k] / chunks:8.0f} cycles per wave-chunk")
 

@@ -85,6 +85,15 @@ hipError_t launch_lz4_decode_lane(const tyche_batch_t &b, uint32_t in_cap, uint3
 hipError_t launch_lz4_decode_quad(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
 // large batches, round 4: one page per lane, chunked, aligned LDS (lz4_decode_lc.hip)
 hipError_t launch_lz4_decode_lc(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
+// The page order of a lane-per-page launch (page_order.hip; the rule is page_order_core.h's): order[]
+// becomes the permutation of [0, count) that sorts every window of `window` consecutive pages (0: the
+// whole batch) by descending bin of min(lengths[i], in_cap), equal bins in page order.  `work` is device
+// scratch of page_order_work_bytes; page_order_fits says whether a batch can be ordered at all (its
+// count fits the 32-bit entries and its window does not make the pass's tables unreasonably large).
+bool page_order_fits(size_t count, uint32_t window);
+size_t page_order_work_bytes(size_t count, uint32_t window);
+hipError_t launch_page_order(const uint32_t *lengths, size_t count, uint32_t in_cap, uint32_t window, uint32_t *order, void *work,
+                             hipStream_t s);
 hipError_t launch_lz4_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 // LZ4_EXACT=1: the bytes and return value of LZ4 1.7.5's LZ4_compress_default (lz4_encode_exact.hip)
 hipError_t launch_lz4_encode_exact(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);

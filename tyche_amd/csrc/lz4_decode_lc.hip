@@ -33,15 +33,26 @@
 //    unflushed tail under 16 bytes, which lets a 128-byte ring carry 88-byte
 //    chunks (lz4_lc_core.h, lc_budget): LDS per wave 14 KiB, 11 waves per CU.
 //
+// A wave runs until its slowest lane is done, and every iteration of its loop is
+// a chunk for all 64 lanes, so which pages share a wave matters: a batch with
+// per-page stream lengths and at least two pages per lane is walked in the order
+// of stream length (page_order.hip, page_order_core.h; the kOrdered
+// instantiation), every other batch by stride.
+//
 // Results are LZ4_decompress_safe's: the decoded size, or -(input bytes
 // consumed)-1 for a malformed stream (stream bytes past its end read as zero,
 // as in the other decoders); on error the page's output is partial.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+
 #include "engine.h"
 #include "lane_ring.h"
 #include "lds_io.h"
 #include "lds_qword.h"
+
+#define PO_HOST 0
+#include "page_order_core.h"
 
 namespace tyche {
 
@@ -60,6 +71,8 @@ namespace tyche {
 // waited for by the stage that follows).
 #ifdef TYCHE_PROFILE
 __device__ unsigned long long g_lcprof[16];
+constexpr unsigned kLcProfWaves = 4096;
+__device__ unsigned g_lcwave[kLcProfWaves];   // counter 0 (the wave loop's iterations) of every wave
 #define LPROF_DECL                                  \
     unsigned long long _pt = clock64(), _acc[16]; \
     for (int _k = 0; _k < 16; _k++) _acc[_k] = 0;
@@ -72,8 +85,10 @@ __device__ unsigned long long g_lcprof[16];
 #define LPROF_ADD(k, v) do { _acc[k] += (unsigned long long)(v); } while (0)
 #define LPROF_END                                                              \
     do {                                                                       \
-        if (lane == 0)                                                         \
+        if (lane == 0) {                                                       \
             for (int _k = 0; _k < 16; _k++) atomicAdd(&g_lcprof[_k], _acc[_k]); \
+            if (blockIdx.x < kLcProfWaves) g_lcwave[blockIdx.x] = (unsigned)_acc[0]; \
+        }                                                                      \
     } while (0)
 #else
 #define LPROF_DECL
@@ -186,13 +201,39 @@ __device__ __forceinline__ void wstore(uint8_t *w16, const LWin &w) {
 // placement knows of it
 constexpr int kVmDrain = 0x0F70;
 
-// starts the lane on page idx or a later one of its stride (pages with an
+// Where a lane finds its pages.  The stride walk takes idx, idx + G, ...; the ordered walk
+// (kOrdered) takes the page that order[] names at the lane's slot of every generation
+// (page_order_core.h: po::slot), so that the lanes of a wave, and the waves, get pages of like
+// cost.  The ordered walk keeps the NEXT generation's page index in `nxt`: its load is issued
+// beside the metadata loads of the page being started and waited for with them, so a page
+// switch costs the same round trips under either walk.
+constexpr uint32_t kNoPage = 0xFFFFFFFFu;
+struct LWalk {
+    const uint32_t *order;
+    uint32_t gen;   // the generation of nxt
+    uint32_t nxt;   // the page of generation `gen`, kNoPage when the lane has none left
+};
+__device__ __forceinline__ uint32_t lwalk_load(const LWalk &W, size_t count, uint32_t lane) {
+    const uint64_t s = po::slot(W.gen, blockIdx.x, lane, gridDim.x, count);
+    return s < count ? W.order[s] : kNoPage;
+}
+
+// starts the lane on page idx or a later one of its walk (pages with an
 // immediate result -- empty capacity, empty stream, over the launch's sizing --
 // are answered here); false when the lane has no page left.  The window of the
 // page's first 64 bytes is loaded synchronously.
+template <bool kOrdered>
 __device__ bool lpage_start(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, size_t idx, size_t G,
-                            LPage &P, uint8_t *w16) {
-    for (; idx < b.count; idx += G) {
+                            LPage &P, uint8_t *w16, LWalk &W, uint32_t lane) {
+    for (;; idx += G) {
+        if (kOrdered) {
+            idx = W.nxt;   // (an index that is no page of the batch ends the walk like kNoPage)
+            if (idx >= b.count) return false;
+            W.gen++;
+            W.nxt = lwalk_load(W, b.count, lane);
+        } else if (idx >= b.count) {
+            return false;
+        }
         const LMeta m = lmeta(b, idx);
         int32_t rv;
         if (m.L > in_cap || m.C > out_cap) {
@@ -211,14 +252,14 @@ __device__ bool lpage_start(const tyche_batch_t &b, uint32_t in_cap, uint32_t ou
             P.tail = 0;
             P.lp = P.lrem = P.moff = P.mrem = P.mtok = P.hdr = P.term = 0;
             wstore(w16, wload(P.in, 0, P.L));
-            // every metadata load done here, where this path waits anyway: a load still in flight
-            // at the loop's back edge would make the compiler drain all stores at the loop's top
+            // every metadata load done here (the ordered walk's next page index among them), where
+            // this path waits anyway: a load still in flight at the loop's back edge would make the
+            // compiler drain all stores at the loop's top
             __builtin_amdgcn_s_waitcnt(kVmDrain);
             return true;
         }
         b.results[idx] = rv;
     }
-    return false;
 }
 
 // 64 bytes of zeros: the window source of a lane with no page (its loads are issued anyway, so that
@@ -254,8 +295,9 @@ __device__ __forceinline__ void lc_far_wait(u32x4 (&fv)[N]) {
 #ifndef LC_WPE
 #define LC_WPE 2   // register budget: waves per SIMD
 #endif
-template <int32_t R>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LC_WPE))) void lz4_decode_lc_kernel(tyche_batch_t b, uint32_t in_cap, uint32_t out_cap) {
+template <int32_t R, bool kOrdered>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LC_WPE))) void lz4_decode_lc_kernel(tyche_batch_t b, uint32_t in_cap, uint32_t out_cap,
+                                                                                                     const uint32_t *order) {
     typedef LCL<R> Lay;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t lane = threadIdx.x;
@@ -273,7 +315,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LC_WPE))) vo
     }
 
     LPage P;
-    bool live = lpage_start(b, in_cap, out_cap, (size_t)blockIdx.x * 64u + lane, G, P, w16);
+    LWalk W{order, 0u, kNoPage};
+    if (kOrdered) W.nxt = lwalk_load(W, b.count, lane);
+    bool live = lpage_start<kOrdered>(b, in_cap, out_cap, (size_t)blockIdx.x * 64u + lane, G, P, w16, W, lane);
     LPROF_DECL
     while (__builtin_amdgcn_ballot_w64(live) != 0) {
         LPROF_ADD(0, 1);
@@ -448,7 +492,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LC_WPE))) vo
                 }
             }
             b.results[P.idx] = rv;
-            live = lpage_start(b, in_cap, out_cap, P.idx + G, G, P, w16);
+            live = lpage_start<kOrdered>(b, in_cap, out_cap, P.idx + G, G, P, w16, W, lane);
         }
         LPROF_MARK(10);   // stage 5: tails, page switch (uniform position: the stamps stay scalar)
         asm volatile("" ::: "memory");
@@ -466,7 +510,24 @@ extern "C" int tyche_debug_lc_profile(unsigned long long *host16, int reset) {
     }
     return hipMemcpyFromSymbol(host16, HIP_SYMBOL(g_lcprof), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : 1;
 }
+// the wave loop's iterations of the last launch's first n waves (n <= 4096)
+extern "C" int tyche_debug_lc_wave_iters(unsigned *host, int n) {
+    if (n < 0 || (unsigned)n > tyche::kLcProfWaves) return 1;
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_lcwave), sizeof(unsigned) * (size_t)n) == hipSuccess ? 0 : 1;
+}
 #endif
+
+// launches that took the ordered walk since the library was loaded (tests: which walk ran)
+static std::atomic<unsigned long long> g_lc_ordered_launches{0};
+extern "C" unsigned long long tyche_debug_lz4_lc_ordered_launches(void) { return g_lc_ordered_launches.load(); }
+
+// The walk's defaults (TYCHE_LZ4_LC_ORDER: 0 = stride walk, 1 = ordered; TYCHE_LZ4_LC_ORDER_WINDOW: pages
+// per window, 0 = the whole batch is one window): what profiles/lz4_order_time.log selected.  ms per
+// decompress call, parent / stride / whole batch / windows of 65,536 / 16,384 / 4,096 pages (medians):
+// 1M x 16 KiB 23.85 / 23.92 / 22.89 / 22.94 / 23.00 / 22.83, 1M x 8 KiB 12.23 / 12.24 / 11.81 / 11.93 / 11.99 /
+// 11.92, 256K x 16 KiB 6.19 / 6.17 / 5.81 / 5.74 / 5.71 / 5.69; the ordering pass (43.5 us at 1M pages) included.
+constexpr long kLcOrder = 1;
+constexpr long kLcOrderWindow = 4096;
 
 hipError_t launch_lz4_decode_lc(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s) {
     if (b.count == 0) return hipSuccess;
@@ -478,26 +539,50 @@ hipError_t launch_lz4_decode_lc(const tyche_batch_t &b, uint32_t in_cap, uint32_
     // pages faster (12.0 vs 13.0 ms per 1M)
     const long r = knob("LZ4_LC_RING", 192);
 #if LC_LINE == 16
-    const void *k = r == 256   ? (const void *)lz4_decode_lc_kernel<256>
-                    : r == 192 ? (const void *)lz4_decode_lc_kernel<192>
-                    : r == 160 ? (const void *)lz4_decode_lc_kernel<160>
-                               : (const void *)lz4_decode_lc_kernel<128>;
+#define LC_PICK(ordered)                                                           \
+    (r == 256   ? (const void *)lz4_decode_lc_kernel<256, ordered>                 \
+     : r == 192 ? (const void *)lz4_decode_lc_kernel<192, ordered>                 \
+     : r == 160 ? (const void *)lz4_decode_lc_kernel<160, ordered>                 \
+                : (const void *)lz4_decode_lc_kernel<128, ordered>)
     const size_t lds = r == 256   ? LCL<256>::total
                        : r == 192 ? LCL<192>::total
                        : r == 160 ? LCL<160>::total
                                   : LCL<128>::total;
 #else   // 64-byte lines need R >= 192 (lc_ring_ok)
-    const void *k = r == 256 ? (const void *)lz4_decode_lc_kernel<256> : (const void *)lz4_decode_lc_kernel<192>;
+#define LC_PICK(ordered) \
+    (r == 256 ? (const void *)lz4_decode_lc_kernel<256, ordered> : (const void *)lz4_decode_lc_kernel<192, ordered>)
     const size_t lds = r == 256 ? LCL<256>::total : LCL<192>::total;
 #endif
+    const void *k = LC_PICK(false);
     const size_t ncu = prepare_launch(k);
     size_t waves = blocks_per_cu(k, 64, lds);
     const long env_waves = knob("LZ4_LC_WAVES", 8);   // (LC_FAR16's 154 VGPRs would allow more at R = 128 / 160: slower)
     if (env_waves > 0) waves = std::min<size_t>(waves, (size_t)env_waves);
-    const size_t grid = std::min<size_t>((b.count + 63) / 64, ncu * waves);
-    void *args[] = {(void *)&b, &in_cap, &out_cap};
+    size_t grid = std::min<size_t>((b.count + 63) / 64, ncu * waves);
+    const long env_grid = knob("LZ4_LC_GRID", 0);   // caps the launch's waves (tests: several generations of a few hundred pages)
+    if (env_grid > 0) grid = std::min<size_t>(grid, (size_t)env_grid);
+    // The ordered walk (page_order_core.h) when there is something to order -- per-page lengths -- and
+    // an order can matter: with a single generation the slowest page decides under either walk.
+    const long env_window = knob("LZ4_LC_ORDER_WINDOW", kLcOrderWindow);
+    const uint32_t window = env_window > 0 && (unsigned long)env_window < b.count ? (uint32_t)env_window : 0u;
+    const bool ordered = knob("LZ4_LC_ORDER", kLcOrder) != 0 && b.src_lengths && b.count >= 2 * grid * 64 &&
+                         page_order_fits(b.count, window);
+    const size_t order_bytes = (b.count * sizeof(uint32_t) + 255u) & ~(size_t)255u;
+    ScratchLease ws(s, ordered ? order_bytes + page_order_work_bytes(b.count, window) : 0);   // order[] | the pass's tables
+    const uint32_t *order = (const uint32_t *)ws.get();
+    if (ordered) {
+        if (!order) return hipErrorOutOfMemory;
+        const hipError_t e =
+            launch_page_order(b.src_lengths, b.count, in_cap, window, (uint32_t *)ws.get(), (uint8_t *)ws.get() + order_bytes, s);
+        if (e != hipSuccess) return e;
+        k = LC_PICK(true);
+        (void)prepare_launch(k);
+        g_lc_ordered_launches++;
+    }
+    void *args[] = {(void *)&b, &in_cap, &out_cap, &order};
     (void)hipLaunchKernel(k, dim3((unsigned)grid), dim3(64), args, lds, s);
     return hipGetLastError();
+#undef LC_PICK
 }
 
 }  // namespace tyche
