@@ -3,6 +3,7 @@
 # rocprofv3 --pmc run per counter set, within the per-block limits (<= 8 SQ, 4 TCC, 4 TCP, 2 TA, 2 TD).
 # Reduced by tools/pmc_round.py into profiles/<tag>_pmc_*.json (with the kernel-source digest).
 #   bash tools/pmc_round.sh <tag>
+# PMC_PASSES="sq1 sq2" runs only the named passes (default: all six); TYCHE_CODEC_LIB picks the library.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 T=${1:-r04}
 O=$R/gpurun_out/pmc_$T
@@ -10,6 +11,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp REPS=1 PAGES=${PAGES:-262144}
 pass() {   # name counters...
   local name=$1; shift
+  [ -z "$PMC_PASSES" ] || [[ " $PMC_PASSES " == *" $name "* ]] || return 0
   timeout -s KILL 90 rocprofv3 --pmc "$@" --output-format csv -d $O/$name -o run -- python3 $R/tools/run_codec.py \
     > $O/$name.log 2>&1 || { echo "pass $name failed"; return 1; }
 }

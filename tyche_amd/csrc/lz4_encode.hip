@@ -40,6 +40,19 @@
 #ifndef TYCHE_LANE_ADDR
 #define TYCHE_LANE_ADDR 1   // lz_parse.h: block windows from per-lane LDS addresses (every page has LDS in front)
 #endif
+// lz_parse.h: the block loop's scalar control code.  One latch is on.  Off, with their numbers in
+// profiles/README.md ("LZ4 encode: block-loop control"; ms per 1M x 16 KiB pages, 55.2-55.3 as shipped):
+// the bit-set hop, 55.1-55.2 with it -- no share of its own beyond the runs' spread --, and one sink call
+// site on top of that, which shrinks the kernel's code by another quarter but ran 55.4-55.5
+#ifndef TYCHE_PARSE_LATCH
+#define TYCHE_PARSE_LATCH 1
+#endif
+#ifndef TYCHE_PARSE_ONE_SINK
+#define TYCHE_PARSE_ONE_SINK 0
+#endif
+#ifndef TYCHE_PARSE_HOP
+#define TYCHE_PARSE_HOP 0
+#endif
 
 #include <algorithm>
 #include <cstdlib>
@@ -508,6 +521,34 @@ __device__ bool write_last_literals(const uint8_t *in, uint32_t anchor, uint32_t
     return true;
 }
 
+#ifndef TYCHE_LZ4_JOINT
+#define TYCHE_LZ4_JOINT 1   // the N-wave kernel's joint sequences by emit_joint (0: through the 64-lane sink and a flush)
+#endif
+// One sequence whose fields are the same in every lane -- a later part's held-back first match
+// `first` after the literal run from prev_end (the previous part's last match end) -- straight to
+// dst + op, the lanes striding its bytes: what the sink emits for this one record (the catch-up of
+// lz4.c:549 included), without the records' loads, the prefix sum and the ring.  false, and
+// nothing written, if it does not fit cap.
+__device__ __forceinline__ bool emit_joint(uint2 first, uint32_t prev_end, const uint8_t *in, uint8_t *dst, uint32_t &op,
+                                           uint32_t cap, uint32_t lane) {
+    const uint32_t pos = first.x & 0xFFFFu, cand = first.x >> 16, len = first.y & 0xFFFFu;
+    const uint32_t back = rfl(lzp::back_at(in, pos, cand));
+    const uint32_t k = min(min(back, pos - prev_end), cand);
+    SeqFields f;
+    f.anchor = prev_end;
+    f.lit = pos - k - prev_end;
+    f.lext = f.lit >= 15 ? (f.lit - 15) / 255 + 1 : 0;
+    f.off = pos - cand;
+    f.mc = len + k - kMinMatch;
+    const uint32_t mext = f.mc >= 15 ? (f.mc - 15) / 255 + 1 : 0;
+    f.token = (min(f.lit, 15u) << 4) | min(f.mc, 15u);
+    f.total = 1 + f.lext + f.lit + 2 + mext;
+    if (op + f.total > cap) return false;
+    for (uint32_t j = lane; j < f.total; j += kWave) dst[op + j] = (uint8_t)seq_byte(f, in, j);
+    op += f.total;
+    return true;
+}
+
 typedef uint32_t u32x4_ua __attribute__((ext_vector_type(4), aligned(1)));
 typedef __attribute__((address_space(1))) u32x4_ua g_u32x4_ua;
 
@@ -828,10 +869,15 @@ __global__ __launch_bounds__(kNW * 64) TYCHE_ENC_WPE_ATTR void lz4_encode_splitn
                         if (lane == 0) hdr->seg[w] = op;
                         continue;
                     }
+#if TYCHE_LZ4_JOINT
+                    const uint2 fr = hdr->first[w];
+                    ok = emit_joint(make_uint2(rfl(fr.x), rfl(fr.y)), cur, in, p.dst, op, p.dst_cap, lane);
+#else
                     if (lane == 0) rec[0] = hdr->first[w];
                     __builtin_amdgcn_wave_barrier();
                     ok = emit_sink_n(rec, 1, cur, in, p.dst, op, p.dst_cap, ring, r, map, lane);
                     if (ok) out_flush_all(ring, r, p.dst, op, lane);
+#endif
                     if (lane == 0) hdr->seg[w] = op;
                     op += rfl(hdr->len[w]);
                     cur = rfl(hdr->cursor[w]);

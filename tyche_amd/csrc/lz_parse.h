@@ -307,6 +307,26 @@ __device__ __forceinline__ uint32_t bucket_of(uint32_t v, uint32_t v2 = 0, uint3
 #ifndef TYCHE_HASH_BYTES
 #define TYCHE_HASH_BYTES 5   // kRepCand (zstd): bytes hashed -- zstd level 1 hashes searchLength bytes
 #endif
+// The scalar control code around parse_page's block loop, set by the including translation unit
+// (lz4_encode.hip sets all three; every other includer compiles the loop as it was).  Records, hand-offs
+// and table inserts are the same in either shape, so the streams are.
+#ifndef TYCHE_PARSE_LATCH
+// 1: the block loop has one latch -- a block without a selectable match and a block that handed its
+// records on both fall through to the one place that advances blk, and `done` is folded into the
+// advance (once no match can start, the next block lies past every position)
+#define TYCHE_PARSE_LATCH 0
+#endif
+#ifndef TYCHE_PARSE_ONE_SINK
+// 1 (needs TYCHE_PARSE_LATCH): a full record batch leaves the block loop and the sink is called at one
+// place for full and last batches alike, so its code is inlined once
+#define TYCHE_PARSE_ONE_SINK 0
+#endif
+#ifndef TYCHE_PARSE_HOP
+// 1: the hop loop sets the selected lane's bit with s_bitset1_b64 and keeps no copy of the lane it
+// came from (the last selected lane is the highest bit of sel: hops only go forward)
+#define TYCHE_PARSE_HOP 0
+#endif
+static_assert(!TYCHE_PARSE_ONE_SINK || TYCHE_PARSE_LATCH, "TYCHE_PARSE_ONE_SINK needs TYCHE_PARSE_LATCH");
 
 //
 // rep (kRepCand, optional): the repeat offsets {R, R2} to start from, and where the final ones go -- a
@@ -341,7 +361,20 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
     // a candidate's window (a position <= mflimit) from its LDS address
     auto win_at = [&](uint32_t x) { return lds_window_at(abase - 4u + ((x + ib) & ~3u), (x + ib) & 3u); };
     PHASE_INIT();
+#if TYCHE_PARSE_LATCH
+    // the block the cursor lies in while matches may still start, the last block of all once they may not
+    uint32_t skip = 0;
+    constexpr uint32_t kFull = kWave - (kMin3 ? 22u : 16u);   // a block adds at most 16 records (22 of >= 3 bytes)
+    // the loop's one exit is its latch, blk > lim: lim is mflimit, and 0 to leave for a hand-off
+    // (the advanced blk is at least 64) -- a second exit would have the compiler merge the two
+    // through flags that every block then sets and tests
+    uint32_t lim = mflimit;
+    bool failed = false;
+    for (;;) {
+    do {
+#else
     for (; !done && blk <= mflimit; blk = max(blk + kWave, cursor & ~(kWave - 1))) {
+#endif
         const uint32_t pos = blk + lane;
         const bool live = pos <= mflimit;
         // ---- this position's window (lanes past mflimit read mflimit's: their
@@ -559,7 +592,11 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
         // (a signed max on the scalar unit: an unsigned saturating subtract goes to a vector ALU)
         const uint32_t at = (uint32_t)max((int32_t)(cursor - blk), 0);
         const uint64_t rem = mall & (~0ull << at);
+#if TYCHE_PARSE_LATCH
+        if (rem != 0) {                                        // else no match starts at or after it
+#else
         if (rem == 0) continue;                                // no match starts at or after it
+#endif
         PHASE_COUNT(10);
         if (kLateProbe) lengths();
         const uint32_t rl = lane + len;                        // the match's end, from blk
@@ -573,8 +610,10 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
             // the hop loop proper: one v_readlane and one taken branch per match
             uint32_t at_li;
             do {
+#if !TYCHE_PARSE_HOP
                 at_li = li;
                 sel |= 1ull << li;
+#endif
                 PHASE_COUNT(9);
                 if (kRepCand) {
                     // repeat history of the selected matches (a new offset shifts it)
@@ -584,8 +623,17 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
                         R = off;
                     }
                 }
+#if TYCHE_PARSE_HOP
+                // (only the bit set is an asm statement: the compiler still sees the v_readlane and pads
+                // the wait states between two dependent ones itself, with one s_nop)
+                static_assert(!TYCHE_PARSE_HOP || !kRepCand, "TYCHE_PARSE_HOP: the single-candidate parse only");
+                asm("s_bitset1_b64 %0, %1" : "+s"(sel) : "s"(rfl(li)));   // (rfl: an "s" operand the compiler cannot prove uniform would be a VGPR)
+#endif
                 li = rdlane(nxt, li);
             } while (li < kWave);
+#if TYCHE_PARSE_HOP
+            at_li = 63u - (uint32_t)__builtin_clzll(sel);
+#endif
             if (li == kWave) {
                 end = blk + at_li + rdlane(len, at_li);
                 break;
@@ -614,6 +662,37 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
         nacc += (uint32_t)__popcll(sel);
         // a block adds at most 16 records (each covers >= 4 positions; 22 of >= 3)
         PHASE(2);
+#if TYCHE_PARSE_LATCH
+        skip = done ? ~(kWave - 1) : cursor & ~(kWave - 1);
+#if TYCHE_PARSE_ONE_SINK
+        lim = nacc > kFull ? 0u : mflimit;
+#else
+        if (nacc > kFull) {
+            __builtin_amdgcn_wave_barrier();
+            if (!sink(rec, nacc, anchor)) {
+                failed = true;
+                lim = 0;
+            }
+            anchor = cursor;
+            nacc = 0;
+            PHASE(3);
+        }
+#endif
+        }
+        blk = max(blk + kWave, skip);
+    } while (blk <= lim);
+    if (failed) return 0xFFFFFFFFu;
+    if (!nacc) break;
+    __builtin_amdgcn_wave_barrier();
+    if (!sink(rec, nacc, anchor)) return 0xFFFFFFFFu;
+    anchor = cursor;
+    nacc = 0;
+    PHASE(3);
+    if (!TYCHE_PARSE_ONE_SINK || blk > mflimit) break;
+    lim = mflimit;
+    }
+    PHASE(4);
+#else
         if (nacc > kWave - (kMin3 ? 22u : 16u) || done) {
             __builtin_amdgcn_wave_barrier();
             if (!sink(rec, nacc, anchor)) return 0xFFFFFFFFu;
@@ -628,6 +707,7 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
         if (!sink(rec, nacc, anchor)) return 0xFFFFFFFFu;
         anchor = cursor;
     }
+#endif
     if (rep) {
         rep[0] = R;
         rep[1] = R2;
