@@ -162,6 +162,32 @@ def test_env_dictionary_that_cannot_serve_fails_every_zstd_host_call(tmp_path):
         assert lines[4].startswith("lz4 ") and lines[4] != "lz4 190", lines[4]
 
 
+def test_each_env_variable_fails_its_own_codec_only(tmp_path):
+    """TYCHE_LZ4_DICT and TYCHE_ZSTD_DICT belong to one slot each: a missing file named in one of
+    them makes tyche_compress_host fail for that variable's codec with that variable's text, and
+    the same call for the other codec gets past its dictionary stage -- TYCHE_E_DEVICE on a machine
+    without a GPU, success on one with it, never TYCHE_E_BAD_ARGS (a fresh child process each)."""
+    code = ("import ctypes, sys, numpy as np\n"
+            "from tyche_amd import _lib\n"
+            "lib = _lib.load()\n"
+            "page = np.zeros(100, np.uint8); out = np.zeros(800, np.uint8); res = (ctypes.c_int32 * 1)()\n"
+            "srcs = (ctypes.c_void_p * 1)(page.ctypes.data); dsts = (ctypes.c_void_p * 1)(out.ctypes.data)\n"
+            "slen, dcap = (ctypes.c_uint32 * 1)(100), (ctypes.c_uint32 * 1)(800)\n"
+            "for codec in (int(sys.argv[1]), int(sys.argv[2])):\n"
+            "    rc = lib.tyche_compress_host(codec, 1, 1, srcs, slen, dsts, dcap, res)\n"
+            "    print(rc, _lib.last_error())\n")
+    for var, own, other in (("TYCHE_LZ4_DICT", 1, ZSTD), ("TYCHE_ZSTD_DICT", ZSTD, 1)):
+        env = {k: v for k, v in os.environ.items() if not k.startswith(("TYCHE_LZ4_DICT", "TYCHE_ZSTD_DICT"))}
+        env.update({var: str(tmp_path / "missing.dict"), "PYTHONPATH": ROOT})
+        p = subprocess.run([sys.executable, "-c", code, str(own), str(other)], env=env, capture_output=True, text=True,
+                           timeout=120)
+        assert p.returncode == 0, p.stderr
+        lines = p.stdout.strip().splitlines()
+        assert len(lines) == 2, p.stdout
+        assert lines[0].startswith("190 ") and (var + ": cannot read") in lines[0], lines[0]
+        assert lines[1].split()[0] in ("0", "199"), lines[1]   # (after a success the text is still the first call's)
+
+
 def test_python_dictionary_still_raises_for_zlib():
     """dictionary= with the zlib codec is a ValueError before anything is launched; Dictionary is the
     codec-neutral name of the handle class and use_zstd_dict is exported."""

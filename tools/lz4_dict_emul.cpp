@@ -50,7 +50,7 @@ extern "C" int lz4_dict_emul_compress(const uint8_t *dict, int D, const uint8_t 
     std::vector<uint8_t> in((size_t)W + 64, 0);
     if (DE) memcpy(in.data(), dict + (D - (int)DE), DE);
     if (L) memcpy(in.data() + DE, src, (size_t)L);
-    // the handle's dictionary table (engine.hip dict_create), then the page's positions over it
+    // the handle's dictionary table (dict.hip dict_create), then the page's positions over it
     std::vector<uint16_t> table(lzd::kTableSizeD, 0);
     auto word = [&](uint32_t p) {
         uint32_t v;

@@ -3,7 +3,8 @@
 // their launchers, the batch's page metadata, and the launch plumbing they
 // share -- grid sizing, dynamic page assignment, scratch leases, knobs.
 // The host batch pipeline is a translation unit of its own, host_batch.hip (its
-// interface to engine.hip: host_batch.h; its chunk plan: host_chunk_core.h).
+// interface to engine.hip: host_batch.h; its chunk plan: host_chunk_core.h), and
+// so is the shared-dictionary layer, dict.hip (its interface to engine.hip: dict.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,17 @@ constexpr int kRunMask = 15;
 __host__ __device__ inline uint32_t lz4_bound(uint32_t n) {
     return n > 0x7E000000u ? 0u : n + n / 255u + 16u;  // LZ4_COMPRESSBOUND, lz4.h:148
 }
+// zstd 1.1.2 ZSTD_compressBound (zstd_compress.c:37): FSE_compressBound(n) + 12
+inline uint32_t zstd_bound(uint32_t n) { return n + (n >> 7) + 512u + 12u; }
+
+// in_cap for a decode batch: the largest stream length (or a bound for unknown lengths)
+inline uint32_t decode_in_cap(const tyche_batch_t &b, uint32_t fallback) {
+    uint32_t in_cap = b.src_lengths ? b.max_src_length : b.src_length;
+    if (b.src_lengths && in_cap == 0) in_cap = fallback;
+    return in_cap;
+}
+// in_cap for an encode batch: the largest page length, 65,535 when per-page lengths come without a maximum
+inline uint32_t encode_in_cap(const tyche_batch_t &b) { return decode_in_cap(b, 65535u); }
 
 // page i of a batch
 struct PageRef {
@@ -107,7 +119,7 @@ hipError_t launch_lz4_encode_hc(const tyche_batch_t &b, uint32_t in_cap, hipStre
 hipError_t launch_lz4_encode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t min_len, hipStream_t s);
 // launches beyond the LDS of the other decoders, up to TYCHE_LZ4_MAX_PAGE (lz4_decode_large.hip)
 hipError_t launch_lz4_decode_large(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
-// A shared LZ4 dictionary's image on one device (engine.hip builds and uploads it once per handle
+// A shared LZ4 dictionary's image on one device (dict.hip builds and uploads it once per handle
 // and device): `dec` is dpad bytes (a multiple of 16) with the dictionary's dlen bytes at their end;
 // `table` the 4,096 16-bit positions of the encoder's read-only dictionary table; `enc` 16 images
 // of enc_stride = enc_len + 16 bytes, image h holding the dictionary's last enc_len = dlen & ~63
@@ -153,7 +165,7 @@ hipError_t launch_zstd_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t 
 // dictionary (ZSTD_compress_usingDict / ZSTD_decompress_usingDict).  The handle and its device image
 // are the LZ4 dictionary's (Lz4DictDev: raw bytes are codec-agnostic); the encoder also takes the
 // handle's seeded table, zstd_dict_seed_bytes() bytes that zstd_dict_seed_table computes on the host
-// from the dictionary's last d.enc_len bytes (engine.hip builds and uploads it at the handle's first
+// from the dictionary's last d.enc_len bytes (dict.hip builds and uploads it at the handle's first
 // zstd compress on a device).  per_page as for LZ4: pages beyond the reach are skipped, their results
 // left alone; else in_cap / out_cap + dlen must not exceed the window.
 size_t zstd_dict_seed_bytes();

@@ -33,6 +33,7 @@
 #include <thread>
 #include <vector>
 
+#include "dict.h"
 #include "engine.h"
 #include "host_batch.h"
 
@@ -365,24 +366,24 @@ namespace {
 thread_local int t_device = -1;
 thread_local std::string t_error;
 
-// TYCHE_LOG_ERRORS=1: every engine failure is also printed to stderr (one
-// "tyche-engine: ..." line), so a caller that drops the status -- list.c:1051
-// keeps going on any rv but 124 -- still leaves a trace (the C1 tests fail on it).
-// The line goes straight to fd 2 (one write): the reference app's stderr is a stdio
-// stream it also prints progress to, and a buffered line would be lost when the
-// app then crashes (the unchanged caller's lost page, test_c1_app.py).
-void log_error(const std::string &m) {
-    if (!knob("LOG_ERRORS", 0)) return;
-    const std::string line = "tyche-engine: " + m + "\n";
-    (void)!write(2, line.data(), line.size());
-}
-
 bool device_is_gfx950(int dev) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
     return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
 }
 }  // namespace
+
+// TYCHE_LOG_ERRORS=1: every engine failure is also printed to stderr (one
+// "tyche-engine: ..." line), so a caller that drops the status -- list.c:1051
+// keeps going on any rv but 124 -- still leaves a trace (the C1 tests fail on it).
+// The line goes straight to fd 2 (one write): the reference app's stderr is a stdio
+// stream it also prints progress to, and a buffered line would be lost when the
+// app then crashes (the unchanged caller's lost page, test_c1_app.py).
+void tyche::log_error(const std::string &m) {
+    if (!knob("LOG_ERRORS", 0)) return;
+    const std::string line = "tyche-engine: " + m + "\n";
+    (void)!write(2, line.data(), line.size());
+}
 
 // ---- shared with the host pipeline (host_batch.h)
 int tyche::fail(const char *what, hipError_t e) {
@@ -449,9 +450,8 @@ int tyche::ensure_device(int dev) {
     return TYCHE_E_OK;
 }
 
-namespace {
 // the device for a thread's device-side work: its pinned one, the rank's, else the first of the set
-int current_device(int *dev) {
+int tyche::current_device(int *dev) {
     if (t_device >= 0 || rank_device() >= 0) {
         *dev = t_device >= 0 ? t_device : rank_device();
         return TYCHE_E_OK;
@@ -462,26 +462,39 @@ int current_device(int *dev) {
     return TYCHE_E_OK;
 }
 
-// codecs with a gfx950 kernel (all of them have one in both directions)
-bool valid_codec(int id) {
-    return id == TYCHE_LZ4_COMPRESSOR_ID || id == TYCHE_ZLIB_COMPRESSOR_ID || id == TYCHE_ZSTD_COMPRESSOR_ID;
-}
-
 // Test hook (TYCHE_FAIL_COMPRESS_EVERY=N or the knob): every Nth encode launch
 // fails as a lost device would, so the callers' TYCHE_E_DEVICE handling
 // (list.c:1051-1060 and the INTEGRATION.md change) can be exercised.
-bool compress_launch_fails() {
+bool tyche::compress_launch_fails() {
     static std::atomic<unsigned long> launches{0};
     const long every = knob("FAIL_COMPRESS_EVERY", 0);
     return every > 0 && (launches.fetch_add(1) + 1) % (unsigned long)every == 0;
 }
 
 // the encoder kernel for a codec id (valid_codec)
-hipError_t launch_encode(int id, const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
+hipError_t tyche::launch_encode(int id, const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
     if (compress_launch_fails()) return hipErrorLaunchFailure;
     if (id == TYCHE_ZSTD_COMPRESSOR_ID) return launch_zstd_encode(b, in_cap, s);
     if (id == TYCHE_ZLIB_COMPRESSOR_ID) return launch_zlib_deflate(b, in_cap, s);
     return launch_lz4_encode(b, in_cap, s);
+}
+
+// Launches, counters and scratch of the device-resident API follow the current
+// device (hipGetDevice); a stream created on another device makes that device
+// current for the call (DeviceGuard puts the caller's back).
+int tyche::stream_device(hipStream_t s) {
+    if (!s) return TYCHE_E_OK;
+    int sd = -1, cur = -1;
+    if (hipStreamGetDevice(s, &sd) != hipSuccess || sd < 0) return TYCHE_E_OK;
+    if (hipGetDevice(&cur) == hipSuccess && cur == sd) return TYCHE_E_OK;
+    hipError_t e = hipSetDevice(sd);
+    return e == hipSuccess ? TYCHE_E_OK : fail("hipSetDevice (stream's device)", e);
+}
+
+namespace {
+// codecs with a gfx950 kernel (all of them have one in both directions)
+bool valid_codec(int id) {
+    return id == TYCHE_LZ4_COMPRESSOR_ID || id == TYCHE_ZLIB_COMPRESSOR_ID || id == TYCHE_ZSTD_COMPRESSOR_ID;
 }
 // The largest page a compress launch may declare (and a host page may have): TYCHE_LZ4_MAX_PAGE
 // for LZ4, whose large-page encoder takes over above 65,535 bytes; 65,535 for zlib and zstd
@@ -516,474 +529,8 @@ std::string codec_msg(int id) {
 
 // zlib 1.2.8 compressBound (compress.c:74-78)
 inline uint32_t zlib_bound(uint32_t n) { return n + (n >> 12) + (n >> 14) + (n >> 25) + 13u; }
-// zstd 1.1.2 ZSTD_compressBound (zstd_compress.c:37): FSE_compressBound(n) + 12
-inline uint32_t zstd_bound(uint32_t n) { return n + (n >> 7) + 512u + 12u; }
-
-// in_cap for a decode batch: the largest stream length (or a bound for unknown lengths)
-inline uint32_t decode_in_cap(const tyche_batch_t &b, uint32_t fallback) {
-    uint32_t in_cap = b.src_lengths ? b.max_src_length : b.src_length;
-    if (b.src_lengths && in_cap == 0) in_cap = fallback;
-    return in_cap;
-}
-// in_cap for an encode batch: the largest page length, 65,535 when per-page lengths come without a maximum
-inline uint32_t encode_in_cap(const tyche_batch_t &b) { return decode_in_cap(b, 65535u); }
 
 constexpr size_t kBulkSmallMax = 64;   // pages of up to 65,536 bytes a raw LZ4 host decode batch may hold beside larger ones
-
-// ------------------------------------------------------ shared LZ4 dictionary
-// A handle is immutable after creation: the bytes, the encoder's dictionary table and the device
-// image (engine.h: Lz4DictDev) are built once on the host; the image is uploaded to a device the
-// first time a launch there needs it, under the handle's lock.  References: the creator's (dropped
-// by tyche_lz4_dict_destroy), the process-wide slot's, and one per host call that runs with the
-// process-wide dictionary.  The last one frees the device copies with hipFree, which returns only
-// once the device has finished the work submitted before it -- a launch still in flight on a
-// caller's stream keeps reading valid memory until it ends.
-}  // namespace
-
-struct tyche_lz4_dict {
-    std::atomic<long> refs{1};
-    uint32_t len = 0, dpad = 0, enc_len = 0, enc_stride = 0;
-    std::vector<uint8_t> image;   // dec (dpad) | table (8 KiB) | enc (16 x enc_stride)
-    std::mutex mu;
-    uint8_t *dev[kMaxDevices] = {};
-    // the zstd encoder's seeded table (engine.h: zstd_dict_seed_table), built at the handle's first zstd
-    // compress and uploaded to a device at its first one there: LZ4-only users pay nothing for it
-    std::vector<uint8_t> zseed;
-    uint8_t *zdev[kMaxDevices] = {};
-};
-namespace {
-constexpr size_t kDictTableBytes = 4096 * sizeof(uint16_t);
-// the encoder's table key (lz_parse.h's hash5 at TYCHE_HASH_LOG 12, lz4_encode_dict.hip): 5 bytes
-inline uint32_t dict_hash(const uint8_t *p) {
-    uint64_t x = 0;
-    memcpy(&x, p, 5);
-    return (uint32_t)((x * 0xCF1BBCDCB7A56463ull) >> 52);
-}
-
-void dict_retain(const tyche_lz4_dict *d) { const_cast<tyche_lz4_dict *>(d)->refs.fetch_add(1); }
-void dict_release(const tyche_lz4_dict *cd) {
-    tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
-    if (!d || d->refs.fetch_sub(1) != 1) return;
-    DeviceGuard keep;
-    for (int i = 0; i < kMaxDevices; i++)
-        if ((d->dev[i] || d->zdev[i]) && hipSetDevice(i) == hipSuccess) {
-            if (d->dev[i]) (void)hipFree(d->dev[i]);
-            if (d->zdev[i]) (void)hipFree(d->zdev[i]);
-        }
-    delete d;
-}
-
-// the handle's image on the current device, uploaded on first use
-int dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, hipError_t *why = nullptr) {
-    tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return (why ? (void)(*why = e) : (void)0), fail("hipGetDevice", e);
-    if (dev < 0 || dev >= kMaxDevices) return (why ? (void)(*why = hipErrorInvalidDevice) : (void)0), fail_msg("selected device out of range");
-    std::lock_guard<std::mutex> g(d->mu);
-    if (!d->dev[dev]) {
-        uint8_t *p = nullptr;
-        if ((e = hipMalloc((void **)&p, d->image.size())) != hipSuccess) {
-            if (why) *why = e;
-            return fail("hipMalloc(dictionary)", e);
-        }
-        if ((e = hipMemcpy(p, d->image.data(), d->image.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-            (void)hipFree(p);
-            if (why) *why = e;
-            return fail("hipMemcpy(dictionary)", e);
-        }
-        d->dev[dev] = p;
-    }
-    out->dec = d->dev[dev];
-    out->table = (const uint16_t *)(d->dev[dev] + d->dpad);
-    out->enc = d->dev[dev] + d->dpad + kDictTableBytes;
-    out->dlen = d->len;
-    out->dpad = d->dpad;
-    out->enc_len = d->enc_len;
-    out->enc_stride = d->enc_stride;
-    return TYCHE_E_OK;
-}
-
-// the handle's image and the zstd encoder's seeded table on the current device
-int zdict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, const void **seed, hipError_t *why = nullptr) {
-    if (int rc = dict_on_device(cd, out, why)) return rc;
-    tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess || dev < 0 || dev >= kMaxDevices) return (why ? (void)(*why = hipErrorInvalidDevice) : (void)0), fail_msg("selected device out of range");
-    std::lock_guard<std::mutex> g(d->mu);
-    if (d->zseed.empty()) {
-        d->zseed.resize(zstd_dict_seed_bytes());
-        zstd_dict_seed_table(d->image.data() + (d->dpad - d->enc_len), d->enc_len, d->zseed.data());
-    }
-    if (!d->zdev[dev]) {
-        uint8_t *p = nullptr;
-        if ((e = hipMalloc((void **)&p, d->zseed.size())) != hipSuccess) {
-            if (why) *why = e;
-            return fail("hipMalloc(dictionary table)", e);
-        }
-        if ((e = hipMemcpy(p, d->zseed.data(), d->zseed.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-            (void)hipFree(p);
-            if (why) *why = e;
-            return fail("hipMemcpy(dictionary table)", e);
-        }
-        d->zdev[dev] = p;
-    }
-    *seed = d->zdev[dev];
-    return TYCHE_E_OK;
-}
-
-tyche_lz4_dict *dict_create(const void *bytes, uint32_t len) {
-    if (!bytes || len == 0 || len > TYCHE_LZ4_DICT_MAX) {
-        t_error = "an LZ4 dictionary holds 1 to TYCHE_LZ4_DICT_MAX (" + std::to_string(TYCHE_LZ4_DICT_MAX) +
-                  ") bytes; got " + (bytes ? std::to_string(len) : std::string("NULL"));
-        return nullptr;
-    }
-    tyche_lz4_dict *d = new tyche_lz4_dict();
-    const uint8_t *src = (const uint8_t *)bytes;
-    d->len = len;
-    d->dpad = (len + 15u) & ~15u;
-    d->enc_len = len & ~63u;
-    d->enc_stride = d->enc_len + 16u;
-    d->image.assign((size_t)d->dpad + kDictTableBytes + 16u * (size_t)d->enc_stride, 0);
-    memcpy(d->image.data() + (d->dpad - len), src, len);
-    // every position of the encoder's part whose 5 hashed bytes lie inside it, the last of equal hashes kept
-    // (window position j = byte j of the part); an empty slot is position 0, as in a zeroed table
-    const uint8_t *tail = src + (len - d->enc_len);
-    uint16_t *table = (uint16_t *)(d->image.data() + d->dpad);
-    for (uint32_t j = 0; j + 5u <= d->enc_len; j++) table[dict_hash(tail + j)] = (uint16_t)j;
-    uint8_t *enc = d->image.data() + d->dpad + kDictTableBytes;
-    for (uint32_t h = 0; h < 16u; h++) memcpy(enc + (size_t)h * d->enc_stride + h, tail, d->enc_len);
-    return d;
-}
-
-// The process-wide dictionary of the host entry points.  Heap state that is never destroyed: a
-// restore dispatcher may still run a batch at exit().
-struct DictSlot {
-    std::mutex mu;
-    const tyche_lz4_dict *d = nullptr;
-    bool env_done = false;
-    std::string env_error;   // TYCHE_LZ4_DICT named a file that cannot serve: every LZ4 host call fails with it
-    // TYCHE_LZ4_DICT_AUTO: the host compress calls collect sample pages (packed in `sample`, their
-    // lengths in `sample_len`) until auto_pages pages or TYCHE_LZ4_TRAIN_MAX_BYTES; the call that
-    // completes the sample takes it away (kAutoTraining) and trains outside the lock
-    enum { kAutoOff, kAutoCollecting, kAutoTraining } auto_state = kAutoOff;
-    uint32_t auto_len = 0;
-    size_t auto_pages = 256;
-    std::vector<uint8_t> sample;
-    std::vector<uint32_t> sample_len;
-    void end_auto() {
-        auto_state = kAutoOff;
-        std::vector<uint8_t>().swap(sample);
-        std::vector<uint32_t>().swap(sample_len);
-    }
-};
-DictSlot &dict_slot() {
-    static DictSlot &s = *new DictSlot();
-    return s;
-}
-// TYCHE_LZ4_DICT=<file>, read once (slot locked)
-void dict_env_locked(DictSlot &S) {
-    if (S.env_done) return;
-    S.env_done = true;
-    const char *path = getenv("TYCHE_LZ4_DICT");
-    if (const char *a = getenv("TYCHE_LZ4_DICT_AUTO"); a && *a) {
-        if (path && *path) {
-            S.env_error = "TYCHE_LZ4_DICT and TYCHE_LZ4_DICT_AUTO are both set: name a dictionary file or have one trained, not both";
-            return;
-        }
-        char *end = nullptr;
-        const long v = strtol(a, &end, 10);
-        if (end == a || *end || v < 128 || v > (long)TYCHE_LZ4_DICT_MAX) {
-            S.env_error = std::string("TYCHE_LZ4_DICT_AUTO: \"") + a + "\" is not a dictionary length of 128 to TYCHE_LZ4_DICT_MAX (" +
-                          std::to_string(TYCHE_LZ4_DICT_MAX) + ") bytes";
-            return;
-        }
-        if (const char *np = getenv("TYCHE_LZ4_DICT_AUTO_PAGES"); np && *np) {
-            const long k = strtol(np, &end, 10);
-            if (end == np || *end || k < 1 || k > (long)TYCHE_LZ4_TRAIN_MAX_PAGES) {
-                S.env_error = std::string("TYCHE_LZ4_DICT_AUTO_PAGES: \"") + np + "\" is not a page count of 1 to TYCHE_LZ4_TRAIN_MAX_PAGES (" +
-                              std::to_string(TYCHE_LZ4_TRAIN_MAX_PAGES) + ")";
-                return;
-            }
-            S.auto_pages = (size_t)k;
-        }
-        S.auto_len = (uint32_t)v;
-        S.auto_state = DictSlot::kAutoCollecting;
-        return;
-    }
-    if (!path || !*path) return;
-    std::vector<uint8_t> buf(TYCHE_LZ4_DICT_MAX + 1u);
-    FILE *f = fopen(path, "rb");
-    if (!f) {
-        S.env_error = std::string("TYCHE_LZ4_DICT: cannot read ") + path;
-        return;
-    }
-    const size_t n = fread(buf.data(), 1, buf.size(), f);
-    fclose(f);
-    if (n == 0 || n > TYCHE_LZ4_DICT_MAX) {
-        S.env_error = std::string("TYCHE_LZ4_DICT: ") + path + (n == 0 ? " is empty" : " is longer than TYCHE_LZ4_DICT_MAX (" +
-                      std::to_string(TYCHE_LZ4_DICT_MAX) + " bytes)");
-        return;
-    }
-    S.d = dict_create(buf.data(), (uint32_t)n);
-}
-// The dictionary an LZ4 host call runs with (retained: the caller releases it), or NULL.
-// TYCHE_E_BAD_ARGS when the environment names a dictionary file that cannot serve.
-int dict_for_host_call(const tyche_lz4_dict **out) {
-    DictSlot &S = dict_slot();
-    std::lock_guard<std::mutex> g(S.mu);
-    dict_env_locked(S);
-    *out = nullptr;
-    if (!S.env_error.empty()) {
-        t_error = S.env_error;
-        return TYCHE_E_BAD_ARGS;
-    }
-    if (S.d) {
-        dict_retain(S.d);
-        *out = S.d;
-    }
-    return TYCHE_E_OK;
-}
-struct DictHold {
-    const tyche_lz4_dict *d = nullptr;
-    ~DictHold() { dict_release(d); }
-};
-// TYCHE_LZ4_DICT_AUTO.  auto_collect copies a host compress call's eligible pages into the sample
-// (slot locked: a memcpy, never the training); the call that completes the sample gets it in *out
-// (dict_len != 0) and trains after compressing its own pages.
-struct AutoSample {
-    uint32_t dict_len = 0;
-    std::vector<uint8_t> data;
-    std::vector<uint32_t> len;
-};
-int dict_exact_conflict();
-int auto_collect(size_t n, const void *const *src, const uint32_t *src_lengths, AutoSample *out) {
-    DictSlot &S = dict_slot();
-    std::lock_guard<std::mutex> g(S.mu);
-    if (S.auto_state == DictSlot::kAutoOff) return TYCHE_E_OK;
-    if (knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
-    if (S.auto_state != DictSlot::kAutoCollecting) return TYCHE_E_OK;
-    bool full = false;
-    for (size_t i = 0; i < n && !full; i++) {
-        const uint32_t L = src_lengths[i];
-        if (L < 128u || (uint64_t)L + S.auto_len > 65536u) continue;
-        if (S.sample.size() + L > TYCHE_LZ4_TRAIN_MAX_BYTES) {
-            full = true;
-            break;
-        }
-        const uint8_t *p = (const uint8_t *)src[i];
-        S.sample.insert(S.sample.end(), p, p + L);
-        S.sample_len.push_back(L);
-        full = S.sample_len.size() >= S.auto_pages;
-    }
-    if (!full) return TYCHE_E_OK;
-    out->dict_len = S.auto_len;
-    out->data.swap(S.sample);
-    out->len.swap(S.sample_len);
-    S.auto_state = DictSlot::kAutoTraining;
-    return TYCHE_E_OK;
-}
-tyche_lz4_dict *train_packed(const uint8_t *data, const uint32_t *lens, size_t n, uint32_t dict_len);
-// Trains on the completed sample and installs the result, unless something was installed (or auto
-// mode ended: tyche_lz4_use_dict) meanwhile.  A failure leaves its reason in t_error and the
-// process plain.
-void auto_train_and_install(const AutoSample &a) {
-    tyche_lz4_dict *d = train_packed(a.data.data(), a.len.data(), a.len.size(), a.dict_len);
-    DictSlot &S = dict_slot();
-    {
-        std::lock_guard<std::mutex> g(S.mu);
-        if (S.auto_state == DictSlot::kAutoTraining) {
-            S.auto_state = DictSlot::kAutoOff;
-            if (d && !S.d) {
-                S.d = d;   // the slot takes the creator's reference
-                d = nullptr;
-            }
-        }
-    }
-    dict_release(d);
-}
-// Why a dictionary upload inside a host-path launch failed.  The launch may run on a fan-out worker
-// thread, whose t_error the caller never sees, and run_host names only "kernel launch": the first
-// reason is kept here and put back into the calling thread's t_error after the batch.
-struct DictUploadNote {
-    std::mutex mu;
-    std::string msg;
-    hipError_t upload(const tyche_lz4_dict *d, Lz4DictDev *img) {
-        hipError_t why = hipErrorUnknown;
-        if (dict_on_device(d, img, &why) == TYCHE_E_OK) return hipSuccess;
-        std::lock_guard<std::mutex> g(mu);
-        if (msg.empty()) msg = t_error;
-        return why;
-    }
-    hipError_t upload(const tyche_lz4_dict *d, Lz4DictDev *img, const void **seed) {
-        hipError_t why = hipErrorUnknown;
-        if (zdict_on_device(d, img, seed, &why) == TYCHE_E_OK) return hipSuccess;
-        std::lock_guard<std::mutex> g(mu);
-        if (msg.empty()) msg = t_error;
-        return why;
-    }
-    int finish(int rc) {
-        if (rc != TYCHE_E_OK && !msg.empty()) {
-            t_error = msg;
-            log_error(t_error);
-        }
-        return rc;
-    }
-};
-int dict_exact_conflict() {
-    t_error = "LZ4_EXACT=1 and an LZ4 dictionary do not combine: exact mode promises LZ4_compress_default's bytes";
-    return TYCHE_E_BAD_ARGS;
-}
-int dict_reach_error(const char *what, uint32_t cap, uint32_t dlen, const char *codec = "LZ4") {
-    t_error = std::string(codec) + " dictionary reach: " + what + " (" + std::to_string(cap) + ") plus the dictionary (" +
-              std::to_string(dlen) + " bytes) exceeds 65536";
-    return TYCHE_E_BAD_ARGS;
-}
-
-// ---- zstd with the same handle.  The bytes are raw content for both codecs; what zstd adds is a
-// rule (bytes that begin with ZSTD_DICT_MAGIC would be a structured dictionary to the reference,
-// which this engine does not implement: refused, never read as raw content) and a process-wide slot
-// of its own, which neither tyche_lz4_use_dict nor the TYCHE_LZ4_DICT* variables touch.
-bool zdict_structured(const tyche_lz4_dict *d) {
-    static const uint8_t magic[4] = {0x37, 0xA4, 0x30, 0xEC};
-    return d->len >= 4u && memcmp(d->image.data() + (d->dpad - d->len), magic, 4) == 0;
-}
-int zdict_structured_error() {
-    t_error = "zstd dictionary: the bytes begin with ZSTD_DICT_MAGIC (37 A4 30 EC), a structured (entropy-table) "
-              "dictionary; structured dictionaries are not supported, only raw content";
-    return TYCHE_E_BAD_ARGS;
-}
-struct ZDictSlot {
-    std::mutex mu;
-    const tyche_lz4_dict *d = nullptr;
-    bool env_done = false;
-    std::string env_error;   // TYCHE_ZSTD_DICT named a file that cannot serve: every zstd host call fails with it
-};
-ZDictSlot &zdict_slot() {
-    static ZDictSlot &s = *new ZDictSlot();   // never destroyed, as dict_slot()
-    return s;
-}
-// TYCHE_ZSTD_DICT=<file>, read once (slot locked)
-void zdict_env_locked(ZDictSlot &S) {
-    if (S.env_done) return;
-    S.env_done = true;
-    const char *path = getenv("TYCHE_ZSTD_DICT");
-    if (!path || !*path) return;
-    std::vector<uint8_t> buf(TYCHE_LZ4_DICT_MAX + 1u);
-    FILE *f = fopen(path, "rb");
-    if (!f) {
-        S.env_error = std::string("TYCHE_ZSTD_DICT: cannot read ") + path;
-        return;
-    }
-    const size_t n = fread(buf.data(), 1, buf.size(), f);
-    fclose(f);
-    if (n == 0 || n > TYCHE_LZ4_DICT_MAX) {
-        S.env_error = std::string("TYCHE_ZSTD_DICT: ") + path + (n == 0 ? " is empty" : " is longer than TYCHE_LZ4_DICT_MAX (" +
-                      std::to_string(TYCHE_LZ4_DICT_MAX) + " bytes)");
-        return;
-    }
-    tyche_lz4_dict *d = dict_create(buf.data(), (uint32_t)n);
-    if (d && zdict_structured(d)) {
-        dict_release(d);
-        S.env_error = std::string("TYCHE_ZSTD_DICT: ") + path + " begins with ZSTD_DICT_MAGIC (37 A4 30 EC), a structured "
-                      "dictionary; structured dictionaries are not supported, only raw content";
-        return;
-    }
-    S.d = d;
-}
-// The dictionary a zstd host call runs with (retained: the caller releases it), or NULL.
-// TYCHE_E_BAD_ARGS when the environment names a dictionary file that cannot serve.
-int zdict_for_host_call(const tyche_lz4_dict **out) {
-    ZDictSlot &S = zdict_slot();
-    std::lock_guard<std::mutex> g(S.mu);
-    zdict_env_locked(S);
-    *out = nullptr;
-    if (!S.env_error.empty()) {
-        t_error = S.env_error;
-        return TYCHE_E_BAD_ARGS;
-    }
-    if (S.d) {
-        dict_retain(S.d);
-        *out = S.d;
-    }
-    return TYCHE_E_OK;
-}
-
-// ---- training (lz4_dict_train.hip).  The rules that need no device come first, so that they read
-// the same with and without one; each names itself and its numbers in t_error.
-std::nullptr_t train_refuse(const std::string &m) {
-    t_error = m;
-    log_error(t_error);
-    return nullptr;
-}
-bool train_args_ok(uint32_t dict_len, size_t count) {
-    if (dict_len < 128u || dict_len > TYCHE_LZ4_DICT_MAX)
-        return train_refuse("LZ4 dictionary training: dict_len (" + std::to_string(dict_len) + ") must be 128 to TYCHE_LZ4_DICT_MAX (" +
-                            std::to_string(TYCHE_LZ4_DICT_MAX) + ") bytes"), false;
-    if (count == 0) return train_refuse("LZ4 dictionary training: count is 0, there are no sample pages"), false;
-    if (count > TYCHE_LZ4_TRAIN_MAX_PAGES)
-        return train_refuse("LZ4 dictionary training: " + std::to_string(count) + " sample pages are more than TYCHE_LZ4_TRAIN_MAX_PAGES (" +
-                            std::to_string(TYCHE_LZ4_TRAIN_MAX_PAGES) + ")"), false;
-    return true;
-}
-std::nullptr_t train_page_too_long(const std::string &which, uint64_t len) {
-    return train_refuse("LZ4 dictionary training: " + which + " (" + std::to_string(len) + " bytes) is above 65535 bytes");
-}
-std::nullptr_t train_too_many_bytes(uint64_t total) {
-    return train_refuse("LZ4 dictionary training: the sample pages hold " + std::to_string(total) +
-                        " bytes, more than TYCHE_LZ4_TRAIN_MAX_BYTES (" + std::to_string(TYCHE_LZ4_TRAIN_MAX_BYTES) + ")");
-}
-// the batch is on the current device, its arguments checked
-tyche_lz4_dict *train_on_device(const tyche_batch_t &b, uint32_t in_cap, uint32_t dict_len, hipStream_t s) {
-    std::vector<uint8_t> bytes(dict_len);
-    TrainResult r;
-    const hipError_t e = train_lz4_dict(b, in_cap, dict_len, s, bytes.data(), &r);
-    if (e != hipSuccess) return fail((std::string("lz4 dictionary training (") + r.step + ")").c_str(), e), nullptr;
-    if (r.too_long)
-        return train_refuse("LZ4 dictionary training: a sample page is longer than the batch's declared maximum (" +
-                            std::to_string(in_cap) + " bytes; at most 65535)");
-    if (r.total_bytes > TYCHE_LZ4_TRAIN_MAX_BYTES) return train_too_many_bytes(r.total_bytes);
-    if (r.dict_len == 0)
-        return train_refuse("LZ4 dictionary training: the sample pages share no content (no 8-byte key occurs in two of the " +
-                            std::to_string(b.count) + " pages), so there is nothing to put into a dictionary");
-    return dict_create(bytes.data(), r.dict_len);
-}
-// n pages packed one after another in `data`
-tyche_lz4_dict *train_packed(const uint8_t *data, const uint32_t *lens, size_t n, uint32_t dict_len) {
-    DeviceGuard keep;
-    int dev = 0;
-    if (current_device(&dev) != TYCHE_E_OK || ensure_device(dev) != TYCHE_E_OK) return nullptr;
-    uint64_t total = 0;
-    uint32_t longest = 0;
-    std::vector<uint64_t> offs(n);
-    for (size_t i = 0; i < n; i++) {
-        offs[i] = total;
-        total += lens[i];
-        longest = std::max(longest, lens[i]);
-    }
-    const size_t data_bytes = ((size_t)total + 15u) & ~(size_t)15u, off_bytes = n * sizeof(uint64_t);
-    uint8_t *dm = nullptr;
-    hipError_t e = hipMalloc((void **)&dm, data_bytes + 16u + off_bytes + n * sizeof(uint32_t));
-    if (e != hipSuccess) return fail("hipMalloc(sample pages)", e), nullptr;
-    uint64_t *d_off = (uint64_t *)(dm + data_bytes + 16u);
-    uint32_t *d_len = (uint32_t *)(dm + data_bytes + 16u + off_bytes);
-    if ((total && (e = hipMemcpy(dm, data, (size_t)total, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (e = hipMemcpy(d_off, offs.data(), off_bytes, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d_len, lens, n * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) {
-        (void)hipFree(dm);
-        return fail("hipMemcpy(sample pages)", e), nullptr;
-    }
-    tyche_batch_t b = {};
-    b.count = n;
-    b.src = dm;
-    b.src_offsets = d_off;
-    b.src_lengths = d_len;
-    b.max_src_length = longest;
-    tyche_lz4_dict *d = train_on_device(b, std::max(longest, 1u), dict_len, nullptr);
-    (void)hipFree(dm);
-    return d;
-}
 
 }  // namespace
 
@@ -1068,19 +615,7 @@ uint32_t tyche_compress_bound(int compressor_id, uint32_t n) {
     return 0;
 }
 
-// ------------------------------------------------------- device-resident API
-// Launches, counters and scratch follow the current device (hipGetDevice); a
-// stream created on another device makes that device current for the call
-// (DeviceGuard puts the caller's back).
-static int stream_device(hipStream_t s) {
-    if (!s) return TYCHE_E_OK;
-    int sd = -1, cur = -1;
-    if (hipStreamGetDevice(s, &sd) != hipSuccess || sd < 0) return TYCHE_E_OK;
-    if (hipGetDevice(&cur) == hipSuccess && cur == sd) return TYCHE_E_OK;
-    hipError_t e = hipSetDevice(sd);
-    return e == hipSuccess ? TYCHE_E_OK : fail("hipSetDevice (stream's device)", e);
-}
-
+// ------------------------------------------------------- device-resident API (stream_device)
 int tyche_compress_batch(int compressor_id, int compressor_level, const tyche_batch_t *batch, void *stream) {
     (void)compressor_level;   // level is fixed at 1 by tyche (src/options.c:68); LZ4 has no level
     if (!batch) return TYCHE_E_BAD_ARGS;
@@ -1173,174 +708,6 @@ uint64_t tyche_pack_plan(size_t n, const int32_t *results, uint32_t max_length, 
     return pack_plan_host(n, results, max_length, align, capacity, state, offsets, lengths);
 }
 
-// ------------------------------------------------- shared LZ4 dictionary API
-tyche_lz4_dict_t *tyche_lz4_dict_create(const void *bytes, uint32_t len) { return dict_create(bytes, len); }
-
-void tyche_lz4_dict_destroy(tyche_lz4_dict_t *d) { dict_release(d); }
-
-uint32_t tyche_lz4_dict_length(const tyche_lz4_dict_t *d) { return d ? d->len : 0u; }
-
-int tyche_lz4_use_dict(const tyche_lz4_dict_t *d) {
-    DictSlot &S = dict_slot();
-    const tyche_lz4_dict *old;
-    {
-        std::lock_guard<std::mutex> g(S.mu);
-        S.env_done = true;   // an explicit choice replaces whatever TYCHE_LZ4_DICT names
-        S.env_error.clear();
-        S.end_auto();        // and ends TYCHE_LZ4_DICT_AUTO: a training still running will not install
-        old = S.d;
-        if (d) dict_retain(d);
-        S.d = d;
-    }
-    dict_release(old);
-    return TYCHE_E_OK;
-}
-
-uint32_t tyche_lz4_dict_bytes(const tyche_lz4_dict_t *d, void *out, uint32_t cap) {
-    if (!d) return 0u;
-    if (out && cap) memcpy(out, d->image.data() + (d->dpad - d->len), std::min(cap, d->len));
-    return d->len;
-}
-
-tyche_lz4_dict_t *tyche_lz4_current_dict(void) {
-    DictSlot &S = dict_slot();
-    std::lock_guard<std::mutex> g(S.mu);
-    dict_env_locked(S);
-    if (S.d) dict_retain(S.d);
-    return const_cast<tyche_lz4_dict *>(S.d);
-}
-
-tyche_lz4_dict_t *tyche_lz4_dict_train_batch(const tyche_batch_t *samples, uint32_t dict_len, void *stream) {
-    if (!samples) return train_refuse("LZ4 dictionary training: samples is NULL");
-    if (!train_args_ok(dict_len, samples->count)) return nullptr;
-    if (!samples->src) return train_refuse("LZ4 dictionary training: samples->src is NULL");
-    const uint32_t in_cap = encode_in_cap(*samples);
-    if (in_cap > 65535u) return train_page_too_long(samples->src_lengths ? "the batch's declared maximum" : "src_length", in_cap);
-    if (!samples->src_lengths && (uint64_t)samples->count * in_cap > TYCHE_LZ4_TRAIN_MAX_BYTES)
-        return train_too_many_bytes((uint64_t)samples->count * in_cap);
-    DeviceGuard keep;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess) return fail_msg("no HIP device available (the codec runs only on the GPU)"), nullptr;
-    if (stream_device((hipStream_t)stream)) return nullptr;
-    return train_on_device(*samples, std::max(in_cap, 1u), dict_len, (hipStream_t)stream);
-}
-
-tyche_lz4_dict_t *tyche_lz4_dict_train_host(size_t n, const void *const *src, const uint32_t *src_lengths,
-                                            uint32_t dict_len) {
-    if (!train_args_ok(dict_len, n)) return nullptr;
-    if (!src || !src_lengths) return train_refuse("LZ4 dictionary training: src or src_lengths is NULL");
-    uint64_t total = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (src_lengths[i] > 65535u) return train_page_too_long("page " + std::to_string(i), src_lengths[i]);
-        total += src_lengths[i];
-    }
-    if (total > TYCHE_LZ4_TRAIN_MAX_BYTES) return train_too_many_bytes(total);
-    std::vector<uint8_t> data((size_t)total);
-    size_t at = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (src_lengths[i]) memcpy(data.data() + at, src[i], src_lengths[i]);
-        at += src_lengths[i];
-    }
-    return train_packed(data.data(), src_lengths, n, dict_len);
-}
-
-int tyche_lz4_compress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream) {
-    if (!d || !batch) return TYCHE_E_BAD_ARGS;
-    if (knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
-    if (batch->count == 0) return TYCHE_E_OK;
-    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
-    const uint32_t in_cap = encode_in_cap(*batch);
-    if ((uint64_t)in_cap + d->len > 65536u) return dict_reach_error("the launch's largest page", in_cap, d->len);
-    DeviceGuard keep;
-    if (int rc = stream_device((hipStream_t)stream)) return rc;
-    Lz4DictDev img;
-    if (int rc = dict_on_device(d, &img)) return rc;
-    hipError_t e = compress_launch_fails() ? hipErrorLaunchFailure   // the FAIL_COMPRESS_EVERY test hook, as launch_encode
-                                           : launch_lz4_encode_dict(*batch, in_cap, img, false, (hipStream_t)stream);
-    if (e != hipSuccess) return fail("lz4 dictionary encode launch", e);
-    return TYCHE_E_OK;
-}
-
-int tyche_lz4_decompress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream) {
-    if (!d || !batch) return TYCHE_E_BAD_ARGS;
-    if (batch->count == 0) return TYCHE_E_OK;
-    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
-    const uint32_t out_cap = batch->dst_capacity;
-    if ((uint64_t)out_cap + d->len > 65536u) return dict_reach_error("the launch's largest capacity", out_cap, d->len);
-    DeviceGuard keep;
-    if (int rc = stream_device((hipStream_t)stream)) return rc;
-    Lz4DictDev img;
-    if (int rc = dict_on_device(d, &img)) return rc;
-    // (a declared stream maximum is only a bound: above the longest stream a 65,536-byte window can
-    // need it is taken as that, and a page whose stream is longer still gets INT32_MIN)
-    const uint32_t in_cap = std::min(decode_in_cap(*batch, lz4_bound(out_cap)), lz4_bound(65536u));
-    hipError_t e = launch_lz4_decode_dict(*batch, in_cap, out_cap, img, false, (hipStream_t)stream);
-    if (e != hipSuccess) return fail("lz4 dictionary decode launch", e);
-    return TYCHE_E_OK;
-}
-
-// ------------------------------------------------- zstd with the shared dictionary
-int tyche_zstd_compress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream) {
-    if (!d || !batch) return TYCHE_E_BAD_ARGS;
-    if (zdict_structured(d)) return zdict_structured_error();
-    if (batch->count == 0) return TYCHE_E_OK;
-    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
-    const uint32_t in_cap = encode_in_cap(*batch);
-    if ((uint64_t)in_cap + d->len > 65536u) return dict_reach_error("the launch's largest page", in_cap, d->len, "zstd");
-    DeviceGuard keep;
-    if (int rc = stream_device((hipStream_t)stream)) return rc;
-    Lz4DictDev img;
-    const void *seed = nullptr;
-    if (int rc = zdict_on_device(d, &img, &seed)) return rc;
-    hipError_t e = compress_launch_fails() ? hipErrorLaunchFailure   // the FAIL_COMPRESS_EVERY test hook, as launch_encode
-                                           : launch_zstd_encode_dict(*batch, in_cap, img, seed, false, (hipStream_t)stream);
-    if (e != hipSuccess) return fail("zstd dictionary encode launch", e);
-    return TYCHE_E_OK;
-}
-
-int tyche_zstd_decompress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream) {
-    if (!d || !batch) return TYCHE_E_BAD_ARGS;
-    if (zdict_structured(d)) return zdict_structured_error();
-    if (batch->count == 0) return TYCHE_E_OK;
-    if (!batch->src || !batch->dst || !batch->results) return TYCHE_E_BAD_ARGS;
-    const uint32_t out_cap = batch->dst_capacity;
-    if ((uint64_t)out_cap + d->len > 65536u) return dict_reach_error("the launch's largest capacity", out_cap, d->len, "zstd");
-    DeviceGuard keep;
-    if (int rc = stream_device((hipStream_t)stream)) return rc;
-    Lz4DictDev img;
-    if (int rc = dict_on_device(d, &img)) return rc;
-    // (a declared stream maximum is only a bound -- a slot width, say: above tyche_compress_bound of a
-    // 65,536-byte window it is taken as that, and a page whose stream is longer still gets INT32_MIN)
-    const uint32_t in_cap = std::min(decode_in_cap(*batch, zstd_bound(out_cap)), zstd_bound(65536u));
-    hipError_t e = launch_zstd_decode_dict(*batch, in_cap, out_cap, img, false, (hipStream_t)stream);
-    if (e != hipSuccess) return fail("zstd dictionary decode launch", e);
-    return TYCHE_E_OK;
-}
-
-int tyche_zstd_use_dict(const tyche_dict_t *d) {
-    if (d && zdict_structured(d)) return zdict_structured_error();
-    ZDictSlot &S = zdict_slot();
-    const tyche_lz4_dict *old;
-    {
-        std::lock_guard<std::mutex> g(S.mu);
-        S.env_done = true;   // an explicit choice replaces whatever TYCHE_ZSTD_DICT names
-        S.env_error.clear();
-        old = S.d;
-        if (d) dict_retain(d);
-        S.d = d;
-    }
-    dict_release(old);
-    return TYCHE_E_OK;
-}
-
-tyche_dict_t *tyche_zstd_current_dict(void) {
-    ZDictSlot &S = zdict_slot();
-    std::lock_guard<std::mutex> g(S.mu);
-    zdict_env_locked(S);
-    if (S.d) dict_retain(S.d);
-    return const_cast<tyche_lz4_dict *>(S.d);
-}
-
 // ----------------------------------------------------------- host batch API
 int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const void *const *src,
                         const uint32_t *src_lengths, void *const *dst, const uint32_t *dst_capacities,
@@ -1354,65 +721,28 @@ int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const
     // LZ4's encoders only store to their destination (never read it back), so their streams may go
     // straight into the pinned staging arena (HOST_DIRECT_OUT=0: stage through HBM and D2H instead)
     const int direct = compressor_id == TYCHE_LZ4_COMPRESSOR_ID && knob("HOST_DIRECT_OUT", 1) ? kDirectAlways : kDirectNone;
-    // LZ4 with a process-wide dictionary: the pages it reaches (length + dictionary <= 65536) take
-    // the dictionary encoder; a chunk that also holds longer pages runs today's launch first, for
-    // their bytes, and the dictionary launch then writes the pages in reach over it.
+    auto plain = [compressor_id](const tyche_batch_t &b, hipStream_t s, bool) {
+        return launch_encode(compressor_id, b, std::max(b.max_src_length, 1u), s);
+    };
+    // LZ4 and zstd with a process-wide dictionary (each codec's own): the reach rule, dict_launch
+    const DictCodec *dc = compressor_id != TYCHE_ZLIB_COMPRESSOR_ID ? &dict_codec(compressor_id) : nullptr;
     DictHold dict;
     AutoSample trained_from;   // TYCHE_LZ4_DICT_AUTO: the sample, when this call completed it
-    if (compressor_id == TYCHE_LZ4_COMPRESSOR_ID) {
-        if (int rc = dict_for_host_call(&dict.d)) return rc;
-        if (dict.d && knob("LZ4_EXACT", 0) != 0) return dict_exact_conflict();
-        if (!dict.d)
-            if (int rc = auto_collect(n, src, src_lengths, &trained_from)) return rc;
-    }
-    // zstd with a process-wide dictionary: the same rule with the zstd slot's dictionary
-    if (compressor_id == TYCHE_ZSTD_COMPRESSOR_ID) {
-        if (int rc = zdict_for_host_call(&dict.d)) return rc;
-        if (const tyche_lz4_dict *d = dict.d) {
-            DictUploadNote note;
-            return note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
-                            [d, &note](const tyche_batch_t &b, hipStream_t s, bool) {
-                                Lz4DictDev img;
-                                const void *seed = nullptr;
-                                if (const hipError_t ue = note.upload(d, &img, &seed)) return ue;
-                                const uint32_t longest = std::max(b.max_src_length, 1u), reach = 65536u - d->len;
-                                if (longest <= reach)
-                                    return compress_launch_fails() ? hipErrorLaunchFailure
-                                                                   : launch_zstd_encode_dict(b, longest, img, seed, false, s);
-                                const hipError_t e = launch_encode(TYCHE_ZSTD_COMPRESSOR_ID, b, longest, s);
-                                if (e != hipSuccess) return e;
-                                return launch_zstd_encode_dict(b, reach, img, seed, true, s);
-                            }, false, direct));
-        }
-    }
-    if (trained_from.dict_len) {
-        // compressed plain like every call before the install, then trained and installed
-        const int rc = run_host(n, src, src_lengths, dst, dst_capacities, results,
-                                [](const tyche_batch_t &b, hipStream_t s, bool) {
-                                    return launch_encode(TYCHE_LZ4_COMPRESSOR_ID, b, std::max(b.max_src_length, 1u), s);
-                                }, false, direct);
-        auto_train_and_install(trained_from);
-        return rc;
-    }
-    if (const tyche_lz4_dict *d = dict.d) {
+    if (dc)
+        if (int rc = dict.get(*dc)) return rc;
+    if (compressor_id == TYCHE_LZ4_COMPRESSOR_ID)
+        if (int rc = lz4_host_compress_rules(dict.d, n, src, src_lengths, &trained_from)) return rc;
+    if (dict.d) {
         DictUploadNote note;
         return note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
-                        [d, &note](const tyche_batch_t &b, hipStream_t s, bool) {
-                            Lz4DictDev img;
-                            if (const hipError_t ue = note.upload(d, &img)) return ue;
-                            const uint32_t longest = std::max(b.max_src_length, 1u), reach = 65536u - d->len;
-                            if (longest <= reach)
-                                return compress_launch_fails() ? hipErrorLaunchFailure
-                                                               : launch_lz4_encode_dict(b, longest, img, false, s);
-                            const hipError_t e = launch_encode(TYCHE_LZ4_COMPRESSOR_ID, b, longest, s);
-                            if (e != hipSuccess) return e;
-                            return launch_lz4_encode_dict(b, reach, img, true, s);
-                        }, false, direct));
+                                    [&](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
+                                        return dict_launch(*dc, false, dict.d, note, b, s, host_dst, plain);
+                                    }, false, direct));
     }
-    return run_host(n, src, src_lengths, dst, dst_capacities, results,
-                          [compressor_id](const tyche_batch_t &b, hipStream_t s, bool) {
-                              return launch_encode(compressor_id, b, std::max(b.max_src_length, 1u), s);
-                          }, false, direct);
+    const int rc = run_host(n, src, src_lengths, dst, dst_capacities, results, plain, false, direct);
+    // (compressed plain like every call before the install, then trained and installed)
+    if (trained_from.dict_len) auto_train_and_install(trained_from);
+    return rc;
 }
 
 int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, const uint32_t *src_lengths,
@@ -1424,27 +754,20 @@ int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, c
                               [](const tyche_batch_t &b, hipStream_t s, bool) {
                                   return launch_zlib_inflate(b, b.dst_capacity, s);
                               }, true);
+    // LZ4 and zstd with a process-wide dictionary (each codec's own): the reach rule, dict_launch
+    const DictCodec &dc = dict_codec(compressor_id);
+    DictHold dict;
+    DictUploadNote note;
+    if (int rc = dict.get(dc)) return rc;
     if (compressor_id == TYCHE_ZSTD_COMPRESSOR_ID) {
-        // With a process-wide zstd dictionary the pages it reaches (capacity + dictionary <= 65536)
-        // take the dictionary decoder; a chunk that also holds larger capacities runs today's launch
-        // first, for them, and the dictionary launch then decodes the pages in reach over whatever
-        // that left.
-        DictHold zdict;
-        if (int rc = zdict_for_host_call(&zdict.d)) return rc;
-        const tyche_lz4_dict *zd = zdict.d;
-        DictUploadNote znote;
-        return znote.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
-                              [zd, &znote](const tyche_batch_t &b, hipStream_t s, bool) {
-                                  if (!zd) return launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
-                                  Lz4DictDev img;
-                                  if (const hipError_t ue = znote.upload(zd, &img)) return ue;
-                                  const uint32_t reach = 65536u - zd->len;
-                                  const uint32_t in_cap = std::min(b.max_src_length, zstd_bound(65536u));
-                                  if (b.dst_capacity <= reach) return launch_zstd_decode_dict(b, in_cap, b.dst_capacity, img, false, s);
-                                  const hipError_t e = launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
-                                  if (e != hipSuccess) return e;
-                                  return launch_zstd_decode_dict(b, in_cap, reach, img, true, s);
-                              }, true));
+        auto plain = [](const tyche_batch_t &b, hipStream_t s, bool) {
+            return launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
+        };
+        return note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
+                                    [&](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
+                                        if (!dict.d) return plain(b, s, host_dst);
+                                        return dict_launch(dc, true, dict.d, note, b, s, host_dst, plain);
+                                    }, true));
     }
     // A capacity above TYCHE_LZ4_MAX_PAGE is refused by the launch of the chunk that holds it, as
     // every capacity beyond the decoders' LDS used to be: TYCHE_E_DEVICE, earlier chunks drained.
@@ -1458,26 +781,15 @@ int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, c
     size_t n_small = 0, n_large = 0;
     for (size_t i = 0; i < n; i++) (dst_capacities[i] <= 65536u ? n_small : n_large)++;
     const bool mixed_bulk = n_large > 0 && n_small > kBulkSmallMax;
-    // With a process-wide dictionary the pages it reaches (capacity + dictionary <= 65536) take the
-    // dictionary decoder; a chunk that also holds larger capacities runs today's launch first, for
-    // them, and the dictionary launch then decodes the pages in reach over whatever that left.
-    DictHold dict;
-    if (int rc = dict_for_host_call(&dict.d)) return rc;
-    const tyche_lz4_dict *d = dict.d;
-    DictUploadNote note;
+    auto plain = [](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
+        return launch_lz4_decode(b, b.max_src_length, b.dst_capacity, s, !host_dst);
+    };
     const int rc = note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
-                          [mixed_bulk, d, &note](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
-                              if (mixed_bulk && b.dst_capacity > 65536u) return hipErrorInvalidValue;
-                              if (!d) return launch_lz4_decode(b, b.max_src_length, b.dst_capacity, s, !host_dst);
-                              Lz4DictDev img;
-                              if (const hipError_t ue = note.upload(d, &img)) return ue;
-                              const uint32_t reach = 65536u - d->len;
-                              const uint32_t in_cap = std::min(b.max_src_length, lz4_bound(65536u));
-                              if (b.dst_capacity <= reach) return launch_lz4_decode_dict(b, in_cap, b.dst_capacity, img, false, s);
-                              const hipError_t e = launch_lz4_decode(b, b.max_src_length, b.dst_capacity, s, !host_dst);
-                              if (e != hipSuccess) return e;
-                              return launch_lz4_decode_dict(b, in_cap, reach, img, true, s);
-                          }, true, knob("HOST_DIRECT_OUT", 1) ? kDirectLz4Decode : kDirectNone));
+                                        [&](const tyche_batch_t &b, hipStream_t s, bool host_dst) {
+                                            if (mixed_bulk && b.dst_capacity > 65536u) return hipErrorInvalidValue;
+                                            if (!dict.d) return plain(b, s, host_dst);
+                                            return dict_launch(dc, true, dict.d, note, b, s, host_dst, plain);
+                                        }, true, knob("HOST_DIRECT_OUT", 1) ? kDirectLz4Decode : kDirectNone));
     if (rc == TYCHE_E_DEVICE && mixed_bulk)
         t_error += " (an LZ4 host batch with a capacity above 65536 bytes beside more than " + std::to_string(kBulkSmallMax) +
                    " pages of at most that is refused: pass the large pages in a call of their own)";

@@ -1,6 +1,6 @@
 // host_batch.h -- internal interface between the C-ABI layer (engine.hip) and the host batch
 // pipeline (host_batch.hip): run_host and what goes with it, and the few things the pipeline
-// needs from engine.hip.
+// and the shared-dictionary layer (dict.hip) need from engine.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +21,8 @@ int fail(const char *what, hipError_t e);
 int fail_msg(const std::string &m);
 const std::string &thread_error();
 void set_thread_error(const std::string &m);
+// TYCHE_LOG_ERRORS=1: the line a failure leaves on stderr (fail and fail_msg write it themselves)
+void log_error(const std::string &m);
 
 uint64_t now_ns();
 
@@ -36,6 +38,15 @@ const DeviceSet &device_set();
 int pinned_device();
 // makes `dev` current on this thread after checking it (cached per device)
 int ensure_device(int dev);
+// the device for a thread's device-side work: its pinned one, the rank's, else the first of the set
+int current_device(int *dev);
+// makes the device of stream s (when it has one) current for a device-resident call
+int stream_device(hipStream_t s);
+
+// the encoder kernel for a codec id; compress_launch_fails is the FAIL_COMPRESS_EVERY test hook,
+// asked once per encode launch (launch_encode asks it itself)
+hipError_t launch_encode(int id, const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
+bool compress_launch_fails();
 
 // Restores the calling thread's current device when it goes out of scope: the
 // host entry points switch devices to run a batch, and a caller (a torch rank

@@ -31,7 +31,8 @@
 //    lanes (a lane storing only its own page's pieces would touch 64 lines per
 //    instruction).  Flushing 16-byte pieces rather than 64-byte lines keeps the
 //    unflushed tail under 16 bytes, which lets a 128-byte ring carry 88-byte
-//    chunks (lz4_lc_core.h, lc_budget): LDS per wave 14 KiB, 11 waves per CU.
+//    chunks (lz4_lc_core.h, lc_budget).  The kernel ships with R = 192: LDS per
+//    wave 18.9 KiB, 8 waves per CU.
 //
 // A wave runs until its slowest lane is done, and every iteration of its loop is
 // a chunk for all 64 lanes, so which pages share a wave matters: a batch with
