@@ -157,6 +157,11 @@ hipError_t launch_pack(const tyche_pack_t &p, hipStream_t s, const char **step);
 uint64_t pack_plan_host(size_t n, const int32_t *results, uint32_t max_length, uint32_t align, uint64_t capacity,
                         uint64_t state[2], uint64_t *offsets, uint32_t *lengths);
 hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
+// ZSTD_HC=1: the same frame format from a better parse -- the 8-way bucket rings of LZ4_HC, both repeat
+// offsets as candidates, the candidate of the highest gain (4 * length - highbit(offset + 1)) and a two-step
+// lazy choice on gains, as pass A1 of the four-pass encode for every batch size (zstd_encode.hip,
+// zstd_hc_core.h; in_cap <= 65535).  launch_zstd_encode goes here when the knob is set.
+hipError_t launch_zstd_encode_hc(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);
 hipError_t launch_zstd_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);

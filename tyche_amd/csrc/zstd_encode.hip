@@ -40,6 +40,9 @@
 #include "huf_enc.h"
 #include "lz_parse.h"
 
+#define ZHC_HOST 0
+#include "zstd_hc_core.h"
+
 namespace tyche {
 namespace {
 
@@ -1169,6 +1172,70 @@ __global__ __launch_bounds__(64) void zstd_parse_dict_kernel(tyche_batch_t b, si
     }
 }
 
+// ---- pass A1 of the high-compression encode (ZSTD_HC=1, launch_zstd_encode_hc below).
+//
+// The parse is zstd_hc_core.h's: 2^9 bucket rings of the 8 latest positions, the nearest lower lane
+// of the block, both repeat offsets, the candidate of the highest gain and the reference's two-step
+// lazy rule on gains, the same text as the host emulator tools/zstd_hc_emul.cpp.  It hands
+// parse_to_area_with the records parse_page would, so the sequences, literals, parse blocks and block
+// sums reach the area as pass A1 always leaves them and passes A2, B and C run unchanged.  One wave
+// per page, the page loop and next-page prefetch of zstd_encode_kernel<true>.
+//
+// LDS: [ rings 8,192 | ring counters 512 | 64 records 512 | copy map 256 | the page's vectors | 64
+// zero bytes ]: 25.3 KiB at 16 KiB pages (6 per CU), 41.3 KiB at 32 KiB (3 per CU), 73.3 KiB at
+// 65,535 bytes (2 per CU).
+constexpr size_t kHcTableBytes = zhc::kTableEntries * sizeof(uint16_t);
+constexpr size_t kHcCntBytes = zhc::kBuckets;
+constexpr size_t kHcFront = kHcTableBytes + kHcCntBytes + kWave * 8 + kWave * 4;   // rings, counters, 64 records, copy map
+static_assert(kHcTableBytes % 16 == 0 && kHcCntBytes % 16 == 0, "rings and counters are cleared as 16-byte vectors");
+__global__ __launch_bounds__(64) void zstd_parse_hc_kernel(tyche_batch_t b, size_t first, size_t count, uint32_t in_cap,
+                                                           unsigned *ctr, uint8_t *ws, size_t ws_page, int32_t *st) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t lane = threadIdx.x;
+    uint16_t *table = (uint16_t *)smem;
+    uint8_t *cnt = smem + kHcTableBytes;
+    uint2 *rec = (uint2 *)(cnt + kHcCntBytes);
+    uint32_t *lmap = (uint32_t *)(rec + kWave);
+    uint8_t *stage = smem + kHcFront;
+    const size_t stride = gridDim.x;
+
+    size_t page = blockIdx.x;   // chunk-local
+    if (page >= count) return;
+    PageRef p = batch_page(b, first + page);
+    uint32_t head = stage_in(p.src, p.src_len <= in_cap ? p.src_len : 0, stage, lane, kWave);
+    for (;;) {
+        const size_t next = ctr ? claim_page(ctr, lane) : page + stride;   // dynamic assignment (engine.h)
+        PageRef pn;
+        TYCHE_NEXT_PAGE(kPrefetchVec);
+        if (next < count) {
+            pn = batch_page(b, first + next);
+            TYCHE_NEXT_PAGE_FETCH(kPrefetchVec, kWave, pn.src, pn.src_len, in_cap, lane)
+        }
+        int32_t rv;
+        if (p.src_len > in_cap) {
+            rv = kResultTooLarge;
+        } else {
+            uint8_t *in = stage + head;
+            // every page starts from empty rings: table and counters are one zeroed range
+            for (uint32_t w = lane; w < (kHcTableBytes + kHcCntBytes) / 16; w += kWave) ((u32x4 *)smem)[w] = u32x4{0, 0, 0, 0};
+            WAVE_SYNC();
+            in[p.src_len + lane] = 0;
+            WAVE_SYNC();
+            const uint32_t L = p.src_len;
+            rv = parse_to_area_with(
+                in, L, ws + page * ws_page, enc_rec_cap(in_cap), lane,
+                [&](auto &sink) { return zhc::parse_page(in, L, table, cnt, rec, sink, lane); }, in, lmap);
+        }
+        if (lane == 0) st[page] = rv;
+        if (next >= count) break;
+        WAVE_SYNC();
+        page = next;
+        p = pn;
+        head = nhead;
+        TYCHE_NEXT_PAGE_INSTALL(kPrefetchVec, kWave, p.src, p.src_len, in_cap, stage, lane)
+    }
+}
+
 // ---- pass A1 on two pipelined waves per page (round 3, TYCHE_ZSTD_PARSE_PIPE=1; not the
 // default: 1,205 vs 1,026 ms per 1M x 32 KiB pages for the one-wave kernel above).  lzp::parse_page_piped: the finder wave hashes block k+1 while
 // the walker wave takes block k's repeat candidates and walk; the records (and so the frames)
@@ -1808,9 +1875,70 @@ extern "C" int tyche_debug_zstd_encode_profile(unsigned long long *host16, int r
 }
 #endif
 
+// TYCHE_ZSTD_HC=1: the four-pass encode with the high-compression parse as pass A1, for every batch
+// size, so that a page's bytes depend on the page alone.  Of the default encoder's knobs only
+// ZSTD_FSE_LOG and ZSTD_SCRATCH_MB reach it.
+hipError_t launch_zstd_encode_hc(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
+    if (b.count == 0) return hipSuccess;
+    if (in_cap > 65535u) return hipErrorInvalidValue;    // 16-bit positions in the parse and sequence records
+    const size_t page_lds = (in_cap + 16u + kPad + 15u) & ~15u;
+    const size_t lds1 = kHcFront + page_lds;
+    const uint32_t logcap = knob("ZSTD_FSE_LOG", 7) <= 6 ? 6u : 7u;
+    const size_t page_bytes = enc_area_bytes(in_cap);
+    size_t budget = (size_t)16 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (b.count * page_bytes > ((size_t)1 << 30) && hipMemGetInfo(&free_b, &total_b) == hipSuccess && ((free_b += scratch_idle_bytes()), true) &&
+        free_b / 4 < budget)
+        budget = free_b / 4;
+    const long mb = knob("ZSTD_SCRATCH_MB", 0);
+    if (mb > 0) budget = (size_t)mb << 20;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(b.count, budget / page_bytes));
+    const size_t st_bytes = (chunk * 4u + 255u) & ~(size_t)255u;
+    ScratchLease lease(s, st_bytes + chunk * page_bytes);
+    if (!lease.get()) return hipErrorOutOfMemory;
+    int32_t *st = (int32_t *)lease.get();
+    uint8_t *ws = (uint8_t *)lease.get() + st_bytes;
+    const void *k1 = (const void *)zstd_parse_hc_kernel;
+    const void *k2 = (const void *)zstd_block_kernel<false>;
+    const size_t ncu = prepare_launch(k1);
+    (void)prepare_launch(k2);
+    (void)prepare_launch((const void *)zstd_fse_kernel);
+    (void)prepare_launch((const void *)zstd_pack_kernel<false>);
+    size_t cu1 = blocks_per_cu(k1, 64, lds1);
+    const size_t cu2 = blocks_per_cu(k2, 64, kA2Lds);
+    const long cap_cu = knob("ZSTD_HC_PAGES_PER_CU", 0);   // (occupancy A/B: resident pages per CU; 0: what fits)
+    if (cap_cu > 0) cu1 = std::min<size_t>(cu1, (size_t)cap_cu);
+    for (size_t first = 0; first < b.count; first += chunk) {
+        const size_t n = std::min(chunk, b.count - first);
+        {
+            const size_t g = std::min<size_t>(n, ncu * cu1);
+            WorkCounter ctr(s, g < n);
+            if (!ctr.get()) return hipErrorOutOfMemory;
+            hipLaunchKernelGGL(zstd_parse_hc_kernel, dim3((unsigned)g), dim3(kWave), lds1, s, b, first, n, in_cap, ctr.get(),
+                               ws, page_bytes, st);
+        }
+        {
+            const size_t g = std::min<size_t>(n, ncu * cu2);
+            WorkCounter ctr(s, g < n);
+            if (!ctr.get()) return hipErrorOutOfMemory;
+            hipLaunchKernelGGL(zstd_block_kernel<false>, dim3((unsigned)g), dim3(kWave), kA2Lds, s, b, first, n, in_cap, ws,
+                               page_bytes, st, ctr.get(), logcap);
+        }
+        hipLaunchKernelGGL(zstd_fse_kernel, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave),
+                           kWave * kFseSlot.words * 4u, s, b, first, n, ws, page_bytes, (const int32_t *)st);
+        hipLaunchKernelGGL(zstd_pack_kernel<false>, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, s, b, first, n,
+                           ws, page_bytes, (const int32_t *)st);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // TYCHE_ZSTD_ENC_SPLIT: 1 (default) four-pass encode for batches of at least
-// TYCHE_ZSTD_SPLIT_MIN (4096) pages, 0 one kernel.
+// TYCHE_ZSTD_SPLIT_MIN (4096) pages, 0 one kernel.  TYCHE_ZSTD_HC=1: every launch to the
+// high-compression encoder above.
 hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s) {
+    if (knob("ZSTD_HC", 0) != 0) return launch_zstd_encode_hc(b, in_cap, s);
     if (b.count == 0) return hipSuccess;
     if (in_cap > 65535u) return hipErrorInvalidValue;    // 16-bit positions in the parse and sequence records
     const size_t page_lds = (in_cap + 16u + kPad + 15u) & ~15u;
