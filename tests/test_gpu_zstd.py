@@ -294,7 +294,7 @@ def test_encode_multiblock_and_incompressible(tc, oracle_mod):
     lh = clen.cpu().numpy()
     assert (lh[8:] <= 32768 + 16).all()
     # 64 KiB - 1 (the device encoders' largest page) of 5-byte words: > 10,000 sequences, several
-    # blocks at every block size the split encoder cuts (TYCHE_ZSTD_AREA_BLK, 4096 by default)
+    # blocks at every block size the split encoder cuts (zstd_encode.hip kZBlk, 4096)
     words = rng.integers(0, 256, (256, 5), dtype=np.uint8)
     host = np.stack([words[rng.integers(0, 256, 65535 // 5 + 1)].reshape(-1)[:65535] for _ in range(4)])
     comp, clen = tc.compress_pages(torch.from_numpy(host).to(DEV), compressor_id=ZSTD)

@@ -440,7 +440,7 @@ static double parse_zstd_fast(uint32_t hbits, uint32_t mls) {
 }
 
 /* the device parse with repeat candidates (lz_parse.h kRepCand): nb buckets x ways, hash of hb bytes;
- * a repeat candidate wins when at most opt_rep_slack bytes shorter than the hash candidate (TYCHE_REP_SLACK) */
+ * a repeat candidate wins when at most opt_rep_slack bytes shorter than the hash candidate (lz_parse.h's kRepSlack) */
 static uint32_t opt_rep_slack = 3;
 static uint32_t opt_parts = 1, opt_seed = 1u << 20, opt_carry_rep = 0, gR = 1, gR2 = 4, opt_warm = 0, opt_all_blocks = 0;
 static double parse_zstd_device(uint32_t nb, uint32_t ways, uint32_t hb) {

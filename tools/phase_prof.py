@@ -1,7 +1,7 @@
 """Per-phase cycle attribution of the LZ4 encoder's parse (profiling build only).
 
-    python /tmp/mkvar.py ph=-DTYCHE_PHASES   # or any build with -DTYCHE_PHASES
-    TYCHE_CODEC_LIB=tyche_amd/libtyche_codec_ph.so PAGES=262144 python tools/phase_prof.py
+    python -c 'from tyche_amd import _build; _build.build(defines=("TYCHE_PHASES",))'
+    TYCHE_CODEC_LIB=tyche_amd/libtyche_codec_phases.so PAGES=262144 python tools/phase_prof.py
 Phases: 0 block scan (hash, lookup, insert, verify, probes, ballot), 1 greedy walk
 (without 5), 2 record append, 3 sink (sequence encoding and byte emission),
 4 loop exit, 5 whole-wave extension of probe-capped matches.  Prints wave cycles per page for each.

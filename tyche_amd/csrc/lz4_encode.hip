@@ -31,27 +31,11 @@
 // 2^10 hash slots (2 KB): the wave's LDS (page 16.4 KB + table + records) drops
 // to 20 KB, one 512-byte granule under 160 KB / 8, so 8 waves per CU instead of
 // 7: 127.7 -> 111.6 ms per 1M pages for ratio 2.635 -> 2.621 (reference 2.647)
-#ifndef TYCHE_LZ4_HASH_LOG
-#define TYCHE_LZ4_HASH_LOG 10
-#endif
-#ifndef TYCHE_HASH_LOG
-#define TYCHE_HASH_LOG TYCHE_LZ4_HASH_LOG
-#endif
-#ifndef TYCHE_LANE_ADDR
-#define TYCHE_LANE_ADDR 1   // lz_parse.h: block windows from per-lane LDS addresses (every page has LDS in front)
-#endif
-// lz_parse.h: the block loop's scalar control code.  One latch is on.  Off, with their numbers in
-// profiles/README.md ("LZ4 encode: block-loop control"; ms per 1M x 16 KiB pages, 55.2-55.3 as shipped):
-// the bit-set hop, 55.1-55.2 with it -- no share of its own beyond the runs' spread --, and one sink call
-// site on top of that, which shrinks the kernel's code by another quarter but ran 55.4-55.5
+#define TYCHE_HASH_LOG 10
+// lz_parse.h: the block loop with one latch (the bit-set hop and the single sink call site tried
+// with it: profiles/README.md, "LZ4 encode: block-loop control")
 #ifndef TYCHE_PARSE_LATCH
 #define TYCHE_PARSE_LATCH 1
-#endif
-#ifndef TYCHE_PARSE_ONE_SINK
-#define TYCHE_PARSE_ONE_SINK 0
-#endif
-#ifndef TYCHE_PARSE_HOP
-#define TYCHE_PARSE_HOP 0
 #endif
 
 #include <algorithm>
@@ -199,36 +183,15 @@ __device__ bool emit_records(const uint2 *rec, uint32_t n, uint32_t anchor, cons
 // reuses emit_records' field area, so the LDS budget (and 8 waves per CU) is
 // unchanged; a sink too large for the ring (long literal runs: the ring is
 // flushed first) still takes emit_records straight to HBM.
-// Output ring size and flush width (round 3, 256K x 16 KiB pages, ms per 1M, three-wave encoder):
-// 1 KiB ring, 256-byte dword flushes 79.3-79.4; 2 KiB, 512-byte 8-byte flushes 78.1; 2 KiB, 1 KiB
-// 16-byte flushes 78.2; 1 KiB, 512-byte flushes 80.2 (more batches overflow the ring).  A wave-wide
-// copy of all long literal runs at once (instead of one run after another) ran 80.5.
-// Round 4: 512-byte rings with dword flushes -- a 3-wave page's LDS drops from 30.5 to 26 KiB (6 pages per
-// CU instead of 5) and, with the 5-waves-per-SIMD register budget (TYCHE_ENC_WPE), encode 77.5 -> 72.2 ms
-// (8-byte flushes with the 512-byte ring: 74.7; without the register budget: 79.0); a sink whose bytes
-// would overflow the ring takes emit_records, whose fields then span the records and the ring.
-#ifndef TYCHE_LZ4_RING
-#define TYCHE_LZ4_RING 512
-#endif
-#ifndef TYCHE_LZ4_FLUSH_VEC
-#define TYCHE_LZ4_FLUSH_VEC 1
-#endif
-constexpr uint32_t kOutRing = TYCHE_LZ4_RING;        // bytes; head is always a multiple of kFlushStep
-constexpr uint32_t kFlushVec = TYCHE_LZ4_FLUSH_VEC;  // dwords per lane per flush step (1, 2 or 4)
-constexpr uint32_t kFlushStep = 4u * kWave * kFlushVec;
-static_assert(kOutRing >= 512 && kOutRing % kFlushStep == 0 && (kOutRing & (kOutRing - 1)) == 0, "ring");
-static_assert(kOutRing + 64u * 8u >= 1024u, "emit_records' fields fit the records and the ring");
-typedef uint32_t u32x2_ua __attribute__((ext_vector_type(2), aligned(1)));
-typedef __attribute__((address_space(1))) u32x2_ua g_u32x2_ua;
-typedef uint32_t u32x4_uaf __attribute__((ext_vector_type(4), aligned(1)));
-typedef __attribute__((address_space(1))) u32x4_uaf g_u32x4_uaf;
-#ifndef TYCHE_LIT_LANE
-#define TYCHE_LIT_LANE 8
-#endif
-constexpr uint32_t kLitLane = TYCHE_LIT_LANE;
-#ifndef TYCHE_LIT_GATHER
-#define TYCHE_LIT_GATHER 1
-#endif   // literal bytes a sequence's lane copies itself (emit_staged)
+// A 512-byte ring flushed a dword per lane (round 4; the 1 and 2 KiB rings and the 8- and 16-byte
+// flushes it replaced are measured in profiles/README.md): a 3-wave page's LDS is 26 KiB, 6 pages per
+// CU.  A sink whose bytes would overflow the ring takes emit_records, whose 1 KiB of fields then
+// spans the records and the ring.
+constexpr uint32_t kOutRing = 512;              // bytes; head is always a multiple of kFlushStep
+constexpr uint32_t kFlushStep = 4u * kWave;     // a dword per lane
+static_assert(kOutRing % kFlushStep == 0 && (kOutRing & (kOutRing - 1)) == 0, "ring");
+static_assert(kOutRing + 64u * 8u == 1024u, "emit_records' fields fit the records and the ring");
+constexpr uint32_t kLitLane = 8;   // literal bytes a sequence's lane copies itself (emit_staged: two gathered dwords)
 struct OutRing {
     uint32_t head, pend;   // wave-uniform: ring position of the first unflushed byte, unflushed bytes
 };
@@ -236,19 +199,8 @@ struct OutRing {
 __device__ __forceinline__ void out_flush_steps(const uint8_t *ring, OutRing &r, uint8_t *dst, uint32_t &op,
                                                 uint32_t lane) {
     while (r.pend >= kFlushStep) {
-        const uint8_t *src = ring + ((r.head + 4u * kFlushVec * lane) & (kOutRing - 1));
-        uint8_t *d = dst + op + 4u * kFlushVec * lane;
-        if (kFlushVec == 4) {
-            *(g_u32x4_uaf *)(uintptr_t)d = *(const u32x4 *)src;
-        } else if (kFlushVec == 2) {
-            const uint2 w = *(const uint2 *)src;
-            u32x2_ua v;
-            v.x = w.x;
-            v.y = w.y;
-            *(g_u32x2_ua *)(uintptr_t)d = v;
-        } else {
-            store_u32_unaligned(d, *(const uint32_t *)src);
-        }
+        const uint8_t *src = ring + ((r.head + 4u * lane) & (kOutRing - 1));
+        store_u32_unaligned(dst + op + 4u * lane, *(const uint32_t *)src);
         op += kFlushStep;
         r.head = (r.head + kFlushStep) & (kOutRing - 1);
         r.pend -= kFlushStep;
@@ -308,10 +260,10 @@ __device__ __forceinline__ bool emit_staged(const uint2 *rec, uint32_t n, uint32
     if (op + r.pend + et > cap) return false;
     if (r.pend + et > kOutRing) {
         out_flush_all(ring, r, dst, op, lane);
-        // emit_records' 64 packed fields (1 KiB): the ring, or for a ring under 1 KiB the records
-        // before it and the ring (every layout puts the 64 records right before the ring; they are
-        // read into registers before the fields are written)
-        uint4 *fld = (uint4 *)(kOutRing >= 1024 ? ring : ring + kOutRing - 1024u);
+        // emit_records' 64 packed fields (1 KiB): the records before the ring and the ring (every
+        // layout puts the 64 records right before the ring; they are read into registers before the
+        // fields are written)
+        uint4 *fld = (uint4 *)(ring + kOutRing - 1024u);
         return emit_records(rec, n, anchor, in, dst, op, cap, map, fld, lane);
     }
     SINK_PHASE(11);
@@ -327,7 +279,6 @@ __device__ __forceinline__ bool emit_staged(const uint2 *rec, uint32_t n, uint32
         // batch's longest run kept every other lane idle (the sink was 56 % of
         // the parse's cycles, tools/phase_prof.py)
         const uint32_t ls = min(lit, kLitLane);
-#if TYCHE_LIT_GATHER
         // the run's first 8 bytes from three aligned dwords (the staged page has 64 zero bytes of
         // padding), then up to 8 byte stores that wait on nothing: the byte-at-a-time copy put one
         // LDS read latency per literal byte on the sink's critical path
@@ -344,9 +295,6 @@ __device__ __forceinline__ bool emit_staged(const uint2 *rec, uint32_t n, uint32
             uint8_t *bp = t < ls ? ring + ((q_lit + t) & m) : map;
             *bp = (uint8_t)((t < 4 ? w0 : w1) >> (8 * (t & 3u)));
         }
-#else
-        for (uint32_t t = 0; t < ls; t++) ring[(q_lit + t) & m] = in[lstart + t];
-#endif
         q = q_lit + lit;
         ring[q & m] = (uint8_t)off;
         ring[(q + 1) & m] = (uint8_t)(off >> 8);
@@ -374,24 +322,21 @@ __device__ __forceinline__ bool emit_staged(const uint2 *rec, uint32_t n, uint32
 }
 #undef SINK_PHASE
 
-#ifndef TYCHE_LZ4_SINK_CALL
-// the sink as a call instead of inlined into the parse: bit 0 for the one-wave kernel (encode_page),
-// bit 1 for the N-wave split kernels.  One wave per page, ms per 1M pages: 8 KiB 70.7 inlined ->
-// 44.7 called, 4 KiB 34.8 -> 21.3 (the inlined sink was round 3's 38 -> 70 ms regression at 8 KiB);
-// the three-wave kernel the other way: 16 KiB 77.9 inlined vs 86.9 called, 8 KiB 41.4 vs 46.6
-#define TYCHE_LZ4_SINK_CALL 1
-#endif
-// the sink as a call (as in round 2)
+// The sink as a call instead of inlined into the parse, for the one-wave kernel (encode_page): ms
+// per 1M pages, 8 KiB 70.7 inlined -> 44.7 called, 4 KiB 34.8 -> 21.3.  The N-wave split kernels
+// inline emit_staged: the three-wave kernel ran 16 KiB 77.9 inlined vs 86.9 called.
 __device__ __noinline__ bool emit_staged_call(const uint2 *rec, uint32_t n, uint32_t anchor, const uint8_t *in, uint8_t *dst,
                                               uint32_t &op, uint32_t cap, uint8_t *ring, OutRing &r, uint8_t *map,
                                               uint32_t lane) {
     return emit_staged(rec, n, anchor, in, dst, op, cap, ring, r, map, lane);
 }
 
+// The N-wave kernels' sink: emit_staged, inlined.  The pass-through stays a function of its own
+// because the compiler inlines through it in another order than into the sink directly, and allocates
+// the split kernels' registers differently: their code is held to what was measured.
 __device__ __forceinline__ bool emit_sink_n(const uint2 *rec, uint32_t n, uint32_t anchor, const uint8_t *in, uint8_t *dst,
                                             uint32_t &op, uint32_t cap, uint8_t *ring, OutRing &r, uint8_t *map,
                                             uint32_t lane) {
-    if (TYCHE_LZ4_SINK_CALL & 2) return emit_staged_call(rec, n, anchor, in, dst, op, cap, ring, r, map, lane);
     return emit_staged(rec, n, anchor, in, dst, op, cap, ring, r, map, lane);
 }
 
@@ -400,22 +345,14 @@ __device__ __forceinline__ bool emit_sink_n(const uint2 *rec, uint32_t n, uint32
 __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, uint8_t *map, uint2 *rec,
                                uint4 *fld, uint8_t *dst, uint32_t cap, uint32_t lane) {
     uint32_t op = 0;
-#ifndef TYCHE_LZ4_STAGED
-#define TYCHE_LZ4_STAGED 1
-#endif
     OutRing r{0u, 0u};
     uint8_t *ring = (uint8_t *)fld;
     auto sink = [&](const uint2 *rr, uint32_t n, uint32_t anchor) -> bool {
-        if ((TYCHE_LZ4_STAGED != 0) & ((TYCHE_LZ4_SINK_CALL & 1) != 0)) return emit_staged_call(rr, n, anchor, in, dst, op, cap, ring, r, map, lane);
-        if (TYCHE_LZ4_STAGED) return emit_staged(rr, n, anchor, in, dst, op, cap, ring, r, map, lane);
-        // emit_records' 1 KiB field area ends where the ring does (as in emit_staged's fallback):
-        // with a ring under 1 KiB it starts in the record array, never past the ring into the page
-        return emit_records(rr, n, anchor, in, dst, op, cap, map,
-                            (uint4 *)(kOutRing >= 1024 ? ring : ring + kOutRing - 1024u), lane);
+        return emit_staged_call(rr, n, anchor, in, dst, op, cap, ring, r, map, lane);
     };
     const uint32_t anchor = lzp::parse_page(in, L, table, rec, lane, sink);
     if (anchor == 0xFFFFFFFFu) return 0;
-    if (TYCHE_LZ4_STAGED) out_flush_all(ring, r, dst, op, lane);
+    out_flush_all(ring, r, dst, op, lane);
     // ---- last literals: in[anchor, L)
     const uint32_t lit = L - anchor;
     const uint32_t lext = lit >= 15 ? (lit - 15) / 255 + 1 : 0;
@@ -455,10 +392,8 @@ __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, u
 // 16 KiB pages: 108.2 -> 93.3 ms per 1M pages (12 waves per CU instead of 8); 8 KiB pages stay on the
 // one-wave kernel (13 waves per CU already: 45.0 vs 57.6 ms split)
 constexpr uint32_t kSplitMin = 12288;
-#ifndef TYCHE_SPLIT_AT
-#define TYCHE_SPLIT_AT 36   // H = L * TYCHE_SPLIT_AT / 64, rounded down to 64 (ms per 1M x 16 KiB pages: 32: 98.7, 34: 94.3, 35: 93.2, 36: 93.3, 38: 95.4, 40: 99.1)
-#endif
-static_assert(TYCHE_SPLIT_AT >= 32 && TYCHE_SPLIT_AT < 64, "B's half must fit its scratch (sized for L / 2 + 64)");
+constexpr uint32_t kSplitAt = 36;   // H = L * kSplitAt / 64, rounded down to 64 (ms per 1M x 16 KiB pages: 32: 98.7, 34: 94.3, 35: 93.2, 36: 93.3, 38: 95.4, 40: 99.1)
+static_assert(kSplitAt >= 32 && kSplitAt < 64, "B's half must fit its scratch (sized for L / 2 + 64)");
 constexpr uint32_t kSplitPrefetch = 8;   // 16-byte vectors per thread prefetched for the next page
 struct SplitHdr {
     uint32_t next_lo, next_hi, next2_lo, next2_hi;
@@ -521,10 +456,7 @@ __device__ bool write_last_literals(const uint8_t *in, uint32_t anchor, uint32_t
     return true;
 }
 
-#ifndef TYCHE_LZ4_JOINT
-#define TYCHE_LZ4_JOINT 1   // the N-wave kernel's joint sequences by emit_joint (0: through the 64-lane sink and a flush)
-#endif
-// One sequence whose fields are the same in every lane -- a later part's held-back first match
+// The N-wave kernel's joint sequences.  One sequence whose fields are the same in every lane -- a later part's held-back first match
 // `first` after the literal run from prev_end (the previous part's last match end) -- straight to
 // dst + op, the lanes striding its bytes: what the sink emits for this one record (the catch-up of
 // lz4.c:549 included), without the records' loads, the prefix sum and the ring.  false, and
@@ -591,7 +523,7 @@ __global__ __launch_bounds__(128, 3) void lz4_encode_split_kernel(tyche_batch_t 
         const uint32_t L = p.src_len;
         const bool fits = L <= in_cap;
         const bool split = fits && L >= kSplitMin;
-        const uint32_t H = (L * TYCHE_SPLIT_AT / 64u) & ~(kWave - 1u);   // A takes a little more than half: B also seeds
+        const uint32_t H = (L * kSplitAt / 64u) & ~(kWave - 1u);   // A takes a little more than half: B also seeds
         uint32_t opA = 0, cursorA = 0;
         bool okA = true;
         OutRing rA{0u, 0u};
@@ -704,10 +636,7 @@ __global__ __launch_bounds__(128, 3) void lz4_encode_split_kernel(tyche_batch_t 
 // no match joins the literal run.  The waves then copy their streams into place.
 // Per page LDS: header + kNW x (table, map, records, ring) + the stage: 31.5 KiB
 // for 4 waves at 16 KiB pages, 5 pages (20 waves) per CU by LDS.
-#ifndef TYCHE_LZ4_SEED
-#define TYCHE_LZ4_SEED 4096   // positions seeded before a part (a multiple of 64)
-#endif
-constexpr uint32_t kSeed = TYCHE_LZ4_SEED;
+constexpr uint32_t kSeed = 4096;   // positions seeded before a part (a multiple of 64) where the launch sets no other
 template <uint32_t kNW>
 struct SplitHdrN {
     uint32_t next_lo, next_hi, next2_lo, next2_hi;
@@ -731,18 +660,11 @@ __host__ __device__ constexpr uint32_t part_scratch(uint32_t in_cap) {   // a pa
 template <uint32_t kNW>
 constexpr uint32_t split_prefetch() { return (16384u / 16u + kNW * kWave - 1u) / (kNW * kWave); }   // 16 KiB per page
 
+// amdgpu_waves_per_eu(5): the split kernels' register budget (round 4, with the 512-byte ring: 72.2 ms
+// per 1M x 16 KiB pages, 79.0 without it; profiles/README.md)
 template <uint32_t kNW, bool kRagged>
-#ifndef TYCHE_ENC_WPE
-#define TYCHE_ENC_WPE 5   // amdgpu_waves_per_eu register budget of the split kernels (4 waves: 87 VGPRs, no spills; 0: none)
-#endif
-#if TYCHE_ENC_WPE > 0
-#define TYCHE_ENC_WPE_ATTR __attribute__((amdgpu_waves_per_eu(TYCHE_ENC_WPE)))
-#else
-#define TYCHE_ENC_WPE_ATTR
-#endif
-__global__ __launch_bounds__(kNW * 64) TYCHE_ENC_WPE_ATTR void lz4_encode_splitn_kernel(tyche_batch_t b, uint32_t in_cap, unsigned *ctr,
-                                                                     uint8_t *ws, uint32_t ws_stride, uint32_t seed,
-                                                                     uint32_t p0) {
+__global__ __launch_bounds__(kNW * 64) __attribute__((amdgpu_waves_per_eu(5))) void lz4_encode_splitn_kernel(
+    tyche_batch_t b, uint32_t in_cap, unsigned *ctr, uint8_t *ws, uint32_t ws_stride, uint32_t seed, uint32_t p0) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr uint32_t kT = kNW * kWave;                 // threads per page
     constexpr uint32_t kPf = split_prefetch<kNW>();       // 16-byte vectors per thread prefetched
@@ -863,21 +785,13 @@ __global__ __launch_bounds__(kNW * 64) TYCHE_ENC_WPE_ATTR void lz4_encode_splitn
                 // layout: part 0's stream, then per later part the joint sequence and its stream
                 uint32_t op = rfl(hdr->len[0]), cur = rfl(hdr->cursor[0]);
                 bool ok = true, tail_done = false;
-                OutRing r{0u, 0u};
                 for (uint32_t w = 1; w < kNW && ok; w++) {
                     if (!rfl(hdr->has_first[w])) {
                         if (lane == 0) hdr->seg[w] = op;
                         continue;
                     }
-#if TYCHE_LZ4_JOINT
                     const uint2 fr = hdr->first[w];
                     ok = emit_joint(make_uint2(rfl(fr.x), rfl(fr.y)), cur, in, p.dst, op, p.dst_cap, lane);
-#else
-                    if (lane == 0) rec[0] = hdr->first[w];
-                    __builtin_amdgcn_wave_barrier();
-                    ok = emit_sink_n(rec, 1, cur, in, p.dst, op, p.dst_cap, ring, r, map, lane);
-                    if (ok) out_flush_all(ring, r, p.dst, op, lane);
-#endif
                     if (lane == 0) hdr->seg[w] = op;
                     op += rfl(hdr->len[w]);
                     cur = rfl(hdr->cursor[w]);

@@ -38,9 +38,6 @@
 
 #define TYCHE_HASH_LOG 12   // lz_parse.h's table in this translation unit: lzd::kHashLogD
 #define TYCHE_PARSE_HASH5 1 // keyed by 5 bytes (lz_parse.h), as the handle's dictionary table is
-#ifndef TYCHE_LANE_ADDR
-#define TYCHE_LANE_ADDR 1   // block windows from per-lane LDS addresses (the records stand in front of the window)
-#endif
 
 #include <algorithm>
 

@@ -34,10 +34,7 @@ constexpr uint32_t kWave = 64;
 #endif
 constexpr uint32_t kHashLog = TYCHE_HASH_LOG;
 constexpr uint32_t kHashSize = 1u << kHashLog;
-#ifndef TYCHE_PROBE_WORDS
-#define TYCHE_PROBE_WORDS 4
-#endif
-constexpr uint32_t kProbeWords = TYCHE_PROBE_WORDS;   // 4-byte words probed per lane beyond MINMATCH
+constexpr uint32_t kProbeWords = 4;   // 4-byte words probed per lane beyond MINMATCH (Window, probe_len)
 constexpr uint32_t kProbe = 4 * kProbeWords;
 
 // Timing-only ablation builds (-DTYCHE_EABLATE=mask; outputs are wrong):
@@ -97,8 +94,9 @@ __device__ __forceinline__ uint32_t lds_word(const uint32_t *A, uint32_t q) {
 struct Window {
     uint32_t back, w0, fw[kProbeWords];
 };
+// The general form, from the page's dword base: pipe_find and parse_page_piped only (parse_page
+// reads its windows with lds_window_at).
 __device__ __forceinline__ Window lds_window(const uint32_t *A, uint32_t q) {
-    static_assert(kProbeWords == 4, "the window holds four probe words");
     const uint32_t i = q >> 2, s = q & 3u;
     const uint32_t dm = A[max(i, 1u) - 1];   // q < 4 only at positions < 4, whose backward probe is unused
     uint32_t d[6];
@@ -114,8 +112,8 @@ __device__ __forceinline__ Window lds_window(const uint32_t *A, uint32_t q) {
 
 // LDS byte address of a pointer into LDS, and a dword pointer from one: the LZ4
 // encoder addresses a lane's windows from a per-lane base fixed for the page
-// (TYCHE_LANE_ADDR below), so a block's window costs one add and one min
-// instead of the nine address instructions of lds_window's general form.
+// (parse_page), so a block's window costs one add and one min instead of the
+// nine address instructions of lds_window's general form.
 typedef const __attribute__((address_space(3))) uint32_t lds_u32_t;
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint8_t *)p;
@@ -160,7 +158,6 @@ __device__ __forceinline__ uint32_t ffbh_raw(uint32_t x) {
 // are equal): the first set bit of the 128-bit difference from one min over per-word bit
 // positions (0xFFFFFFFF stays above every real one), 15 instructions instead of 24
 __device__ __forceinline__ uint32_t probe_len(const uint32_t (&a)[kProbeWords], const uint32_t (&b)[kProbeWords]) {
-    static_assert(kProbeWords == 4, "four probe words");
     const uint32_t t0 = ffbl_raw(a[0] ^ b[0]), t1 = ffbl_raw(a[1] ^ b[1]) | 32u, t2 = ffbl_raw(a[2] ^ b[2]) | 64u,
                    t3 = ffbl_raw(a[3] ^ b[3]) | 96u;
     return 4u + (min(min(t0, t1), min(min(t2, t3), 128u)) >> 3);
@@ -222,7 +219,12 @@ __device__ __forceinline__ void decode_record(const uint2 *rec, uint32_t n, uint
     offset = pos - cand;
 }
 
-// Greedy parse of in[0, L) (LDS, 64 zero bytes after).  table: kHashSize 16-bit
+// Greedy parse of in[0, L) (LDS, 64 zero bytes after, and LDS in front of the
+// page: windows are read from LDS addresses, lds_window_at, a lane's own from a
+// base fixed for the page, candidates' from the page's base, and a window below
+// position 4 reads the dword before the page -- unused, such positions and
+// candidates take no backward extension.  Lanes past mflimit read mflimit's
+// dword: unused values, inserts that no lookup follows).  table: kHashSize 16-bit
 // slots, zeroed by the caller.  rec: 64 uint2 records.  sink(rec, n, anchor)
 // consumes n >= 1 records whose literal runs start at `anchor`, and returns
 // false to abort.  Returns the anchor where the last literal run starts, or
@@ -248,30 +250,30 @@ __device__ __forceinline__ void decode_record(const uint2 *rec, uint32_t n, uint
 // holding earlier positions already (the split LZ4 encoder's second wave); the
 // first literal run starts at `start`.
 //
-// kWays (deflate: 4): the table is 2 * kHashSize (TYCHE_WAYS_SCALE) 16-bit slots in buckets of
+// kWays (deflate: 4): the table is kWaysScale * kHashSize 16-bit slots in buckets of
 // kWays positions, most recent first (table_slots<kWays>()); every position
 // verifies all of its bucket's candidates and keeps the longest match (the
 // most recent of equally long ones) -- deflate_fast's hash chain cut at 4
 // (max_chain 4 at level 1, deflate.c:134), with a bucket standing in for the
 // chain.  Lanes of one block that share a bucket insert in unspecified order
 // (one of them wins), as the single-slot table does.
-#ifndef TYCHE_HASH3
-#define TYCHE_HASH3 1   // kMin3 with buckets: hash 3 bytes (deflate's MIN_MATCH), not 4
-#endif
-#ifndef TYCHE_WAYS_SCALE
-#define TYCHE_WAYS_SCALE 2   // bucketed tables hold TYCHE_WAYS_SCALE * kHashSize slots
-#endif
-// kRepCand (zstd) with 2 or 4 ways: 2 * TYCHE_ZSTD_BUCKETS slots in buckets of
+// kMin3 with buckets hashes 3 bytes (deflate's MIN_MATCH), not 4.
+constexpr uint32_t kWaysScale = 2;   // bucketed tables hold kWaysScale * kHashSize slots
+// kRepCand (zstd) with 2 or 4 ways: 2 * kZstdBuckets slots in buckets of
 // kWays, a bucket count that is not a power of two -- 3,712 slots (7,424 bytes)
 // keep a 32 KiB page's parse at 40,848 bytes of LDS, 4 waves per CU
 // (zstd_encode.hip); the bucket is the high product of the hash
-#ifndef TYCHE_ZSTD_BUCKETS
-#define TYCHE_ZSTD_BUCKETS 1856
-#endif
+constexpr uint32_t kZstdBuckets = 1856;
+// kRepCand (zstd): bytes hashed -- zstd level 1 hashes searchLength bytes
+constexpr uint32_t kHashBytes = 5;
+// kRepCand: a repeat candidate wins when at most this many bytes shorter than the hash candidate:
+// a repeat offset costs a few bits instead of ~10-14 (slack 0 / 2 / 3 / 4 measured in
+// profiles/README.md, round 3; tools/parse_sim.c zfse put 3 at level 1's ratio)
+constexpr uint32_t kRepSlack = 3;
 template <int kWays, bool kRepCand = false>
 __host__ __device__ constexpr uint32_t table_slots() {
-    return kRepCand && (kWays == 2 || kWays == 4) ? 2u * TYCHE_ZSTD_BUCKETS
-                                                  : kWays > 1 ? TYCHE_WAYS_SCALE * kHashSize : kHashSize;
+    return kRepCand && (kWays == 2 || kWays == 4) ? 2u * kZstdBuckets
+                                                  : kWays > 1 ? kWaysScale * kHashSize : kHashSize;
 }
 
 template <int kWays>
@@ -282,52 +284,23 @@ __device__ __forceinline__ uint32_t bucket_of(uint32_t v, uint32_t v2 = 0, uint3
     if (nbytes > 4) {   // 5 or 6 bytes: zstd's fast parse hashes searchLength bytes (ZSTD_hashPtr)
         const uint64_t x = ((uint64_t)(v2 & (nbytes == 5 ? 0xFFu : 0xFFFFu)) << 32) | v;
         const uint64_t hx = x * 0xCF1BBCDCB7A56463ull;
-        if (kWays == 2 || kWays == 4) return (uint32_t)(((hx >> 32) * (uint64_t)(2u * TYCHE_ZSTD_BUCKETS / kWays)) >> 32);
+        if (kWays == 2 || kWays == 4) return (uint32_t)(((hx >> 32) * (uint64_t)(2u * kZstdBuckets / kWays)) >> 32);
         return (uint32_t)(hx >> (64 - lg));
     }
     return (v * 2654435761u) >> (32 - lg);
 }
-#ifndef TYCHE_PW_PREFETCH
-// 1: parse_page loads the next block's window ahead, with the current block's candidate
-// windows.  Measured (round 3, 1M x 16 KiB LZ4 pages): 85.0 ms off, 85.9-86.1 on; zlib 645 /
-// 650 -- the LDS latency it hides is not what bounds the parse, and its 6 VGPRs cost.  Off.
-#define TYCHE_PW_PREFETCH 0
-#endif
-#ifndef TYCHE_LANE_ADDR
-// 1: parse_page's windows from LDS addresses (lds_window_at): a lane's own window from a base
-// fixed for the page, candidates' from the page's base.  Lanes past mflimit read mflimit's dword
-// (the LZ4 encoder with their own shift: unused values, inserts that no lookup follows); a window
-// below position 4 reads the dword before the page (unused: such positions and candidates take no
-// backward extension), so every caller keeps LDS in front of the page.
-#define TYCHE_LANE_ADDR 1
-#endif
-#ifndef TYCHE_SINK_BACK
-#define TYCHE_SINK_BACK 1   // zstd: backward extension computed by the sinks (decode_record with `in`)
-#endif
-#ifndef TYCHE_HASH_BYTES
-#define TYCHE_HASH_BYTES 5   // kRepCand (zstd): bytes hashed -- zstd level 1 hashes searchLength bytes
-#endif
 // The scalar control code around parse_page's block loop, set by the including translation unit
-// (lz4_encode.hip sets all three; every other includer compiles the loop as it was).  Records, hand-offs
+// (lz4_encode.hip sets it; every other includer compiles the loop as it was).  Records, hand-offs
 // and table inserts are the same in either shape, so the streams are.
 #ifndef TYCHE_PARSE_LATCH
 // 1: the block loop has one latch -- a block without a selectable match and a block that handed its
 // records on both fall through to the one place that advances blk, and `done` is folded into the
-// advance (once no match can start, the next block lies past every position)
+// advance (once no match can start, the next block lies past every position).
+// Not neutral for the other includers: with 1, zlib_deflate_kernel goes from 211 to 220 VGPRs and
+// gains 8 bytes of private segment, and the zstd parse kernels gain 2 to 4 SGPR spills each -- making
+// it the only shape is a speed experiment, not a clean-up.
 #define TYCHE_PARSE_LATCH 0
 #endif
-#ifndef TYCHE_PARSE_ONE_SINK
-// 1 (needs TYCHE_PARSE_LATCH): a full record batch leaves the block loop and the sink is called at one
-// place for full and last batches alike, so its code is inlined once
-#define TYCHE_PARSE_ONE_SINK 0
-#endif
-#ifndef TYCHE_PARSE_HOP
-// 1: the hop loop sets the selected lane's bit with s_bitset1_b64 and keeps no copy of the lane it
-// came from (the last selected lane is the highest bit of sel: hops only go forward)
-#define TYCHE_PARSE_HOP 0
-#endif
-static_assert(!TYCHE_PARSE_ONE_SINK || TYCHE_PARSE_LATCH, "TYCHE_PARSE_ONE_SINK needs TYCHE_PARSE_LATCH");
-
 //
 // rep (kRepCand, optional): the repeat offsets {R, R2} to start from, and where the final ones go -- a
 // part of a split parse (zstd_encode.hip) warms them up by parsing the bytes before it.
@@ -346,9 +319,6 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
     uint32_t blk = start;    // current 64-position block
     uint32_t R = rep ? rep[0] : 1u, R2 = rep ? rep[1] : 4u;   // repeat offsets 1 and 2 (kRepCand): zstd's initial {1, 4}
     bool done = false;
-    Window pwn{};                       // TYCHE_PW_PREFETCH: the next block's window, loaded ahead
-    uint32_t pwn_blk = 0xFFFFFFFFu;     // the block it belongs to (none yet)
-    constexpr bool kLaneAddr = TYCHE_LANE_ADDR && !TYCHE_PW_PREFETCH;
     const uint32_t abase = rfl(lds_addr(A));
     const uint32_t la = abase + ((lane + ib) & ~3u) - 4u;              // this lane's window at block 0
     const uint32_t la_max = abase + ((mflimit + ib) & ~3u) - 4u;       // mflimit's window
@@ -365,12 +335,11 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
     // the block the cursor lies in while matches may still start, the last block of all once they may not
     uint32_t skip = 0;
     constexpr uint32_t kFull = kWave - (kMin3 ? 22u : 16u);   // a block adds at most 16 records (22 of >= 3 bytes)
-    // the loop's one exit is its latch, blk > lim: lim is mflimit, and 0 to leave for a hand-off
-    // (the advanced blk is at least 64) -- a second exit would have the compiler merge the two
+    // the loop's one exit is its latch, blk > lim: lim is mflimit, and 0 to leave after a sink that
+    // failed (the advanced blk is at least 64) -- a second exit would have the compiler merge the two
     // through flags that every block then sets and tests
     uint32_t lim = mflimit;
     bool failed = false;
-    for (;;) {
     do {
 #else
     for (; !done && blk <= mflimit; blk = max(blk + kWave, cursor & ~(kWave - 1))) {
@@ -382,17 +351,16 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
         // then insert this block's positions.  Every lane takes part, branch-free:
         // lanes past mflimit only exist in the last block, and no lookup follows
         // their inserts.
-        const Window pw = kLaneAddr ? lds_window_at(min(la + blk, la_max), kExactDead && !live ? msh : lsh)
-                          : (TYCHE_PW_PREFETCH && pwn_blk == blk) ? pwn : lds_window(A, (live ? pos : mflimit) + ib);
+        const Window pw = lds_window_at(min(la + blk, la_max), kExactDead && !live ? msh : lsh);
         const uint32_t v = pw.w0;
         constexpr uint32_t vm = kMin3 ? 0xFFFFFFu : 0xFFFFFFFFu;   // the bytes a candidate must match
         uint32_t cands[kWays];
         if (kWays == 1) {
-            const uint32_t h = kRepCand && TYCHE_HASH_BYTES > 4
-                                   ? (uint32_t)(((((uint64_t)(pw.fw[0] & (TYCHE_HASH_BYTES == 5 ? 0xFFu : 0xFFFFu)) << 32) | v) *
+            const uint32_t h = kRepCand && kHashBytes > 4
+                                   ? (uint32_t)(((((uint64_t)(pw.fw[0] & (kHashBytes == 5 ? 0xFFu : 0xFFFFu)) << 32) | v) *
                                                  0xCF1BBCDCB7A56463ull) >> (64 - kHashLog))
                                    : TYCHE_PARSE_HASH5 ? hash5(v, pw.fw[0]) : hash4(v);
-            if (kLaneAddr && !kRepCand) {
+            if (!kRepCand) {
                 lds_u16_t *slot = (lds_u16_t *)(uintptr_t)slot_addr(tbase, h);
                 cands[0] = *slot;
                 __builtin_amdgcn_wave_barrier();
@@ -404,8 +372,8 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
             }
         } else if (kWays == 2) {
             uint32_t *T = (uint32_t *)table;
-            const uint32_t h = kRepCand ? bucket_of<kWays>(v, pw.fw[0], TYCHE_HASH_BYTES)
-                                        : bucket_of<kWays>(kMin3 && TYCHE_HASH3 ? v & 0xFFFFFFu : v);
+            const uint32_t h = kRepCand ? bucket_of<kWays>(v, pw.fw[0], kHashBytes)
+                                        : bucket_of<kWays>(kMin3 ? v & 0xFFFFFFu : v);
             const uint32_t bk = T[h];
             cands[0] = bk & 0xFFFFu;
             cands[kWays > 1 ? 1 : 0] = bk >> 16;
@@ -413,8 +381,8 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
             T[h] = pos | (bk << 16);
         } else if (kWays == 4) {
             uint2 *T = (uint2 *)table;
-            const uint32_t h = kRepCand ? bucket_of<kWays>(v, pw.fw[0], TYCHE_HASH_BYTES)
-                                        : bucket_of<kWays>(kMin3 && TYCHE_HASH3 ? v & 0xFFFFFFu : v);
+            const uint32_t h = kRepCand ? bucket_of<kWays>(v, pw.fw[0], kHashBytes)
+                                        : bucket_of<kWays>(kMin3 ? v & 0xFFFFFFu : v);
             const uint2 bk = T[h];
             cands[0] = bk.x & 0xFFFFu;
             cands[kWays > 1 ? 1 : 0] = bk.x >> 16;
@@ -428,7 +396,7 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
             // distinct candidates than 4 ways over 2^10 buckets (tools/parse_sim.c: 16 KiB
             // pages 4.29 -> 4.35 in the cost model, zlib level 1's own parse 4.34)
             uint4 *T = (uint4 *)table;
-            const uint32_t h = bucket_of<kWays>(kMin3 && TYCHE_HASH3 ? v & 0xFFFFFFu : v);
+            const uint32_t h = bucket_of<kWays>(kMin3 ? v & 0xFFFFFFu : v);
             const uint4 bk = T[h];
             cands[0] = bk.x & 0xFFFFu;
             cands[kWays > 1 ? 1 : 0] = bk.x >> 16;
@@ -446,23 +414,23 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
         // to kProbe bytes) and backward probe (up to 4 bytes).  A candidate is a
         // position <= mflimit, so the window stays inside the page's zero pad.
         uint32_t cand = cands[0];
-        Window cw = kLaneAddr ? win_at(cand) : lds_window(A, cand + ib);
+        Window cw = win_at(cand);
         // deflate (kMin3): a candidate beyond the 32 KiB window cannot be coded; rejecting it here
         // lets a nearer bucket entry win (pages over 32 KiB)
         bool ok = live & (cand < pos) & (!kMin3 || pos - cand <= 32768u) & (((cw.w0 ^ v) & vm) == 0u);
         // one hash candidate and nothing else (LZ4): the probe waits until a match is known to
         // start at or after the cursor (kLateProbe), otherwise the candidates compare lengths here
         constexpr bool kLateProbe = kWays == 1 && !kRepCand && !kMin3;
-        // the LZ4 encoder and the zstd encoder (TYCHE_SINK_BACK) take the backward extension in
-        // their sinks; not deflate, whose distance-4 candidate takes none by construction
-        constexpr bool kSinkBack = kLateProbe || (TYCHE_SINK_BACK && kRepCand && !kMin3);
+        // the LZ4 encoder and the zstd encoder take the backward extension in their sinks
+        // (decode_record with `in`); not deflate, whose distance-4 candidate takes none by construction
+        constexpr bool kSinkBack = kLateProbe || (kRepCand && !kMin3);
         uint32_t n = kLateProbe ? 0u : probe_len(pw.fw, cw.fw);
         if (kMin3 && cw.w0 != v) n = 3u;
 #pragma unroll
         for (int w = 1; w < kWays; w++) {
             // older bucket entries: taken only when strictly longer
             const uint32_t cw2 = cands[w];
-            const Window ww = kLaneAddr ? win_at(cw2) : lds_window(A, cw2 + ib);
+            const Window ww = win_at(cw2);
             const bool okw = live & (cw2 < pos) & (!kMin3 || pos - cw2 <= 32768u) & (((ww.w0 ^ v) & vm) == 0u);
             uint32_t nw = probe_len(pw.fw, ww.fw);
             if (kMin3 && ww.w0 != v) nw = 3u;
@@ -472,15 +440,6 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
                 n = nw;
                 ok = true;
             }
-        }
-        if (TYCHE_PW_PREFETCH) {
-            // the next block's window goes out with this block's candidate windows: its LDS
-            // latency overlaps this block's compares and walk instead of heading the next
-            // block's chain (window -> hash -> table -> candidate window).  A walk that
-            // jumps past the next block (a match running beyond it) reloads.
-            const uint32_t np = blk + kWave + lane;
-            pwn = lds_window(A, (np <= mflimit ? np : mflimit) + ib);
-            pwn_blk = blk + kWave;
         }
         if (kMin3) {
             // distance 4 straight from this position's window (arrays of 4-byte
@@ -505,33 +464,23 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
         if (kRepCand) {
             // the repeat-offset candidate (consecutive windows: cheap loads)
             const uint32_t rc = pos >= R ? pos - R : 0u;
-            const Window rw = kLaneAddr ? win_at(min(rc, mflimit)) : lds_window(A, min(rc, mflimit) + ib);
+            const Window rw = win_at(min(rc, mflimit));
             rok = live & (pos >= R) & (((rw.w0 ^ v) & vm) == 0u);
             uint32_t rn = probe_len(pw.fw, rw.fw);
             if (kMin3 && rw.w0 != v) rn = 3u;
-#ifndef TYCHE_REP_SLACK
-// a repeat candidate wins when at most this many bytes shorter than the hash candidate: a repeat
-// offset costs a few bits instead of ~10-14 (round 3, 64K bench pages: slack 0 / 2 / 3 / 4 ratio
-// 4.676 / 4.708 / 4.709 / 4.704 at 16 KiB, 4.947 / 4.988 / 4.989 / 4.981 at 32 KiB, encode time
-// unchanged; tools/parse_sim.c zfse put 3 at level 1's ratio)
-#define TYCHE_REP_SLACK 3
-#endif
             // repeat offset 2 (the other offset of two alternating ones)
             const uint32_t rc2 = pos >= R2 ? pos - R2 : 0u;
-            const Window rw2 = kLaneAddr ? win_at(min(rc2, mflimit)) : lds_window(A, min(rc2, mflimit) + ib);
-#ifndef TYCHE_REP2
-#define TYCHE_REP2 1
-#endif
-            const bool rok2 = TYCHE_REP2 && live & (pos >= R2) & (((rw2.w0 ^ v) & vm) == 0u) & (R2 != R);
+            const Window rw2 = win_at(min(rc2, mflimit));
+            const bool rok2 = live & (pos >= R2) & (((rw2.w0 ^ v) & vm) == 0u) & (R2 != R);
             uint32_t rn2 = probe_len(pw.fw, rw2.fw);
             if (kMin3 && rw2.w0 != v) rn2 = 3u;
-            if (rok && (!ok || rn + TYCHE_REP_SLACK >= n)) {
+            if (rok && (!ok || rn + kRepSlack >= n)) {
                 cand = rc;
                 cw = rw;
                 n = rn;
                 ok = true;
             }
-            if (rok2 && (!ok || rn2 + TYCHE_REP_SLACK >= n) && !(rok && rn >= rn2)) {
+            if (rok2 && (!ok || rn2 + kRepSlack >= n) && !(rok && rn >= rn2)) {
                 cand = rc2;
                 cw = rw2;
                 n = rn2;
@@ -576,10 +525,7 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
                       : kLateProbe ? __builtin_amdgcn_ballot_w64(live) & __builtin_amdgcn_ballot_w64(cand < pos) &
                                          __builtin_amdgcn_ballot_w64(((cw.w0 ^ v) & vm) == 0u)
                                    : __ballot(ok);
-#ifndef TYCHE_REP_NEXT
-#define TYCHE_REP_NEXT 1
-#endif
-        if (kRepCand && TYCHE_REP_NEXT) {
+        if (kRepCand) {
             // zstd's fast parse tries the repeat offset at ip+1 before the hash
             // candidate at ip (zstd_compress.c:951-958): a position whose
             // successor has a repeat match starts no match of its own unless
@@ -610,10 +556,8 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
             // the hop loop proper: one v_readlane and one taken branch per match
             uint32_t at_li;
             do {
-#if !TYCHE_PARSE_HOP
                 at_li = li;
                 sel |= 1ull << li;
-#endif
                 PHASE_COUNT(9);
                 if (kRepCand) {
                     // repeat history of the selected matches (a new offset shifts it)
@@ -623,17 +567,8 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
                         R = off;
                     }
                 }
-#if TYCHE_PARSE_HOP
-                // (only the bit set is an asm statement: the compiler still sees the v_readlane and pads
-                // the wait states between two dependent ones itself, with one s_nop)
-                static_assert(!TYCHE_PARSE_HOP || !kRepCand, "TYCHE_PARSE_HOP: the single-candidate parse only");
-                asm("s_bitset1_b64 %0, %1" : "+s"(sel) : "s"(rfl(li)));   // (rfl: an "s" operand the compiler cannot prove uniform would be a VGPR)
-#endif
                 li = rdlane(nxt, li);
             } while (li < kWave);
-#if TYCHE_PARSE_HOP
-            at_li = 63u - (uint32_t)__builtin_clzll(sel);
-#endif
             if (li == kWave) {
                 end = blk + at_li + rdlane(len, at_li);
                 break;
@@ -664,9 +599,6 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
         PHASE(2);
 #if TYCHE_PARSE_LATCH
         skip = done ? ~(kWave - 1) : cursor & ~(kWave - 1);
-#if TYCHE_PARSE_ONE_SINK
-        lim = nacc > kFull ? 0u : mflimit;
-#else
         if (nacc > kFull) {
             __builtin_amdgcn_wave_barrier();
             if (!sink(rec, nacc, anchor)) {
@@ -677,19 +609,16 @@ __device__ inline uint32_t parse_page(const uint8_t *in, uint32_t L, uint16_t *t
             nacc = 0;
             PHASE(3);
         }
-#endif
         }
         blk = max(blk + kWave, skip);
     } while (blk <= lim);
     if (failed) return 0xFFFFFFFFu;
-    if (!nacc) break;
-    __builtin_amdgcn_wave_barrier();
-    if (!sink(rec, nacc, anchor)) return 0xFFFFFFFFu;
-    anchor = cursor;
-    nacc = 0;
-    PHASE(3);
-    if (!TYCHE_PARSE_ONE_SINK || blk > mflimit) break;
-    lim = mflimit;
+    if (nacc) {
+        __builtin_amdgcn_wave_barrier();
+        if (!sink(rec, nacc, anchor)) return 0xFFFFFFFFu;
+        anchor = cursor;
+        nacc = 0;
+        PHASE(3);
     }
     PHASE(4);
 #else
@@ -747,7 +676,7 @@ __device__ __forceinline__ void pipe_find(const uint32_t *A, uint32_t ib, uint32
     const Window pw = lds_window(A, (live ? pos : mflimit) + ib);
     const uint32_t v = pw.w0;
     uint32_t *T = (uint32_t *)table;
-    const uint32_t h = bucket_of<2>(v, pw.fw[0], TYCHE_HASH_BYTES);
+    const uint32_t h = bucket_of<2>(v, pw.fw[0], kHashBytes);
     const uint32_t bk = T[h];
     __builtin_amdgcn_wave_barrier();
     T[h] = pos | (bk << 16);
@@ -822,7 +751,7 @@ __device__ uint32_t parse_page_piped(const uint8_t *in, uint32_t L, uint16_t *ta
             }
             const uint32_t rc2 = pos >= R2 ? pos - R2 : 0u;
             const Window rw2 = lds_window(A, min(rc2, mflimit) + ib);
-            const bool rok2 = TYCHE_REP2 && live & (pos >= R2) & (rw2.w0 == v) & (R2 != R);
+            const bool rok2 = live & (pos >= R2) & (rw2.w0 == v) & (R2 != R);
             uint32_t rn2 = 4u + kProbe;
 #pragma unroll
             for (int k = (int)kProbeWords - 1; k >= 0; k--) {
@@ -833,13 +762,13 @@ __device__ uint32_t parse_page_piped(const uint8_t *in, uint32_t L, uint16_t *ta
                 const uint32_t x = pw.back ^ cb;
                 return pos < 4 || c < 4 ? 0u : x ? (__builtin_clz(x) >> 3) : 4u;
             };
-            if (rok && (!ok || rn + TYCHE_REP_SLACK >= n)) {
+            if (rok && (!ok || rn + kRepSlack >= n)) {
                 cand = rc;
                 back = back_of(rc, rw.back);
                 n = rn;
                 ok = true;
             }
-            if (rok2 && (!ok || rn2 + TYCHE_REP_SLACK >= n) && !(rok && rn >= rn2)) {
+            if (rok2 && (!ok || rn2 + kRepSlack >= n) && !(rok && rn >= rn2)) {
                 cand = rc2;
                 back = back_of(rc2, rw2.back);
                 n = rn2;
@@ -852,10 +781,8 @@ __device__ uint32_t parse_page_piped(const uint8_t *in, uint32_t L, uint16_t *ta
             const bool capped = pos + n == e && e < matchlimit;
             // ---- the walk (parse_page's)
             uint64_t mall = __ballot(ok);
-            if (TYCHE_REP_NEXT) {
-                const uint64_t mrep = __ballot(rok);
-                mall &= ~(mrep >> 1) | mrep;
-            }
+            const uint64_t mrep = __ballot(rok);
+            mall &= ~(mrep >> 1) | mrep;
             const uint32_t at = cursor > blk ? cursor - blk : 0u;
             const uint64_t rem = mall & (~0ull << at);
             if (rem != 0) {

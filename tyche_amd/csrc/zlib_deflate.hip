@@ -35,27 +35,16 @@
 #include "lds_io.h"
 #include "huf_enc.h"
 #include "lz_parse.h"
-#ifndef TYCHE_ZLIB_REP
-#define TYCHE_ZLIB_REP 0
-#endif
-#ifndef TYCHE_ZLIB_MIN3
-#define TYCHE_ZLIB_MIN3 1
-#endif
-// The sinks' page pointer for decode_record: the parse leaves the backward extension to its sinks
-// (lz_parse.h kSinkBack) without 3-byte matches -- one-way, or repeat candidates -- so A/B builds of
-// those (TYCHE_ZLIB_MIN3=0 with TYCHE_ZLIB_WAYS=1 or TYCHE_ZLIB_REP=1) hand the page over and keep
-// the catch-up; the default parse keeps the extension in its records
-#define ZLIB_SINK_IN(in) ((!TYCHE_ZLIB_MIN3 && ((TYCHE_ZLIB_WAYS == 1 && !TYCHE_ZLIB_REP) || (TYCHE_SINK_BACK && TYCHE_ZLIB_REP))) ? (in) : nullptr)
-#ifndef TYCHE_ZLIB_WAYS
-#define TYCHE_ZLIB_WAYS 8   // candidates per hash bucket (lz_parse.h kWays; 4 before round 3)
-#endif
 
 namespace tyche {
 namespace {
 
 using lzp::kHashSize;
 using lzp::kWave;
-constexpr int kWays = TYCHE_ZLIB_WAYS;
+// the parse (lz_parse.h parse_page<kRep, kMin3, kWays>): no repeat candidates, matches from 3 bytes
+// on, 8 candidates per hash bucket (4 before round 3)
+constexpr bool kRep = false, kMin3 = true;
+constexpr int kWays = 8;
 constexpr uint32_t kTableSlots = lzp::table_slots<kWays>();
 constexpr uint32_t kPad = 64;
 constexpr uint32_t kStageWords = 128;
@@ -289,11 +278,12 @@ __device__ int32_t encode_fixed1(const uint8_t *in, uint32_t L, uint32_t adler, 
     if (ok) {
         auto sink = [&](const uint2 *r, uint32_t n, uint32_t anc) -> bool {
             uint32_t ls, ll, ml, off;
-            lzp::decode_record(r, n, anc, lane, ls, ll, ml, off, ZLIB_SINK_IN(in));
+            // (without the page: the distance-4 candidate takes no backward extension, so the records carry it)
+            lzp::decode_record(r, n, anc, lane, ls, ll, ml, off);
             if (off > 32768u) { ll += ml; ml = 0; }     // beyond the deflate window: literals
             return code_runs(o, in, n, ls, ll, ml, off, map, lane);
         };
-        anchor = lzp::parse_page<TYCHE_ZLIB_REP != 0, TYCHE_ZLIB_MIN3 != 0, kWays>(in, L, table, rec, lane, sink);
+        anchor = lzp::parse_page<kRep, kMin3, kWays>(in, L, table, rec, lane, sink);
         ok = anchor != 0xFFFFFFFFu;
     }
     if (ok) ok = code_runs(o, in, 1, anchor, L - anchor, 0, 1, map, lane);   // last literals
@@ -381,13 +371,13 @@ __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, u
     auto sink = [&](const uint2 *r, uint32_t n, uint32_t anc) -> bool {
         if (nrec + n > room) return false;
         uint32_t ls, ll, ml, off;
-        lzp::decode_record(r, n, anc, lane, ls, ll, ml, off, ZLIB_SINK_IN(in));
+        lzp::decode_record(r, n, anc, lane, ls, ll, ml, off);
         if (off > 32768u) { ll += ml; ml = 0; off = 1; }     // beyond the deflate window: literals
         if (lane < n) recs[-1 - (int32_t)(nrec + lane)] = make_uint2(ls | (ll << 16), ml | (off << 16));
         nrec += n;
         return true;
     };
-    const uint32_t anchor = lzp::parse_page<TYCHE_ZLIB_REP != 0, TYCHE_ZLIB_MIN3 != 0, kWays>(in, L, table, rec, lane, sink);
+    const uint32_t anchor = lzp::parse_page<kRep, kMin3, kWays>(in, L, table, rec, lane, sink);
     if (anchor == 0xFFFFFFFFu || nrec + 1u > room)
         return encode_fixed1(in, L, adler, table, map, rec, stage, dst, cap, lane);
     if (lane == 0) recs[-1 - (int32_t)nrec] = make_uint2(anchor | ((L - anchor) << 16), 1u << 16);   // last literals

@@ -65,10 +65,7 @@ __device__ unsigned long long g_seprof[16];
 #endif
 
 using lzp::kHashSize;
-#ifndef TYCHE_ZSTD_WAYS
-#define TYCHE_ZSTD_WAYS 2   // candidates per hash bucket (lz_parse.h kWays)
-#endif
-constexpr int kZWays = TYCHE_ZSTD_WAYS;
+constexpr int kZWays = 2;   // candidates per hash bucket (lz_parse.h kWays)
 constexpr uint32_t kTableSlots = lzp::table_slots<kZWays, true>();
 using lzp::kWave;
 constexpr uint32_t kPad = 64;
@@ -380,9 +377,6 @@ __device__ __forceinline__ void resolve_repeats(const Enc &e, uint32_t n, uint32
         uint32_t rc;
         if (ll) rc = off == r0b ? 1u : off == r1b ? 2u : off == r2b ? 3u : 0u;
         else rc = off == r1b ? 1u : off == r2b ? 2u : 0u;
-#ifdef TYCHE_NO_RESOLVE
-        rc = 0;   // timing ablation: raw offsets only
-#endif
         if (i < n) {
             const uint32_t ml = r.y & 0xFFFFu, ofcode = rc ? rc : off + 3u;
             const SeqCode c = seq_code(ll, ml, ofcode);
@@ -877,7 +871,7 @@ __device__ __forceinline__ int32_t encode_page(const uint8_t *in, uint32_t L, ui
     e.lit = nullptr;
     auto sink = [&](const uint2 *r, uint32_t n, uint32_t anchor) -> bool {
         uint32_t ls, ll, ml, off;
-        lzp::decode_record(r, n, anchor, lane, ls, ll, ml, off, TYCHE_SINK_BACK ? in : nullptr);
+        lzp::decode_record(r, n, anchor, lane, ls, ll, ml, off, in);
         if (lane < n) seq[e.nseq + lane] = make_uint2(ll | (off << 16), ml);
         e.nseq += n;
         const uint2 lastr = r[n - 1];
@@ -904,10 +898,7 @@ __device__ __forceinline__ int32_t encode_page(const uint8_t *in, uint32_t L, ui
 // block, which halves pass A2's per-block Huffman and FSE table work (1M x 32 KiB:
 // encode 855 -> 793 ms, decode 308 -> 296 ms, ratio 4.946 -> 4.940; 16 KiB pages,
 // mostly one block already, unchanged -- profiles/r03_zstd_block_size_ab.log)
-#ifndef TYCHE_ZSTD_AREA_BLK
-#define TYCHE_ZSTD_AREA_BLK 4096
-#endif
-constexpr uint32_t kZBlk = TYCHE_ZSTD_AREA_BLK;
+constexpr uint32_t kZBlk = 4096;
 static_assert(kZBlk >= kWave && (65536u / 4u + kZBlk - 1u) / kZBlk + 1u <= kMaxBlk, "area blocks");
 
 // Pass A1: the parse of one page (LDS, 64 zero bytes after) into the area: the
@@ -986,7 +977,7 @@ __device__ __forceinline__ int32_t parse_to_area(const uint8_t *in, uint32_t L, 
     return parse_to_area_with(
         in, L, area, rec_cap, lane,
         [&](auto &sink) { return lzp::parse_page<true, false, kW>(in, L, table, rec, lane, sink); },
-        TYCHE_SINK_BACK ? in : nullptr, map);
+        in, map);
 }
 
 // Pass A2: frame header and every block of the page from the area (the page
@@ -1166,7 +1157,7 @@ __global__ __launch_bounds__(64) void zstd_parse_dict_kernel(tyche_batch_t b, si
             rv = parse_to_area_with(
                 in, W, ws + page * ws_page, enc_rec_cap(in_cap), lane,
                 [&](auto &sink) { return lzp::parse_page<true, false, kZWays>(in, W, table, rec, lane, sink, DE); },
-                TYCHE_SINK_BACK ? in : nullptr, lmap, DE);
+                in, lmap, DE);
         }
         if (lane == 0) st[page] = rv;
     }
@@ -1321,10 +1312,7 @@ __global__ __launch_bounds__(128) void zstd_parse_pipe_kernel(tyche_batch_t b, s
 // wave 0 cuts the list into parse blocks of kZBlk sequences.  Repeat candidates
 // restart at zstd's {1, 4} in each part; the repeat codes themselves are
 // assigned by A2 over the whole list, as before.
-#ifndef TYCHE_ZSTD_SEED
-#define TYCHE_ZSTD_SEED 8192   // positions seeded before a part (multiple of 64)
-#endif
-constexpr uint32_t kZSeed = TYCHE_ZSTD_SEED;
+constexpr uint32_t kZSeed = 8192;   // positions seeded before a part (multiple of 64)
 constexpr uint32_t kZWarm = 256;   // bytes parsed (and dropped) before a part, for its repeat offsets
 template <uint32_t kNW>
 struct ZSplitHdr {
@@ -1404,7 +1392,7 @@ __global__ __launch_bounds__(kNW * 64) void zstd_parse_split_kernel(tyche_batch_
                 auto hash_at = [&](uint32_t blk) {
                     const lzp::lds_u32_t *P = (const lzp::lds_u32_t *)(uintptr_t)(la + blk);
                     const uint32_t d0 = P[0], d1 = P[1], d2 = P[2];
-                    return lzp::bucket_of<kZWays>(lzp::word_at(d0, d1, ls), lzp::word_at(d1, d2, ls), TYCHE_HASH_BYTES);
+                    return lzp::bucket_of<kZWays>(lzp::word_at(d0, d1, ls), lzp::word_at(d1, d2, ls), lzp::kHashBytes);
                 };
                 auto insert = [&](uint32_t h, uint32_t pos) {
                     const uint32_t bk = T[h];
@@ -1431,7 +1419,7 @@ __global__ __launch_bounds__(kNW * 64) void zstd_parse_split_kernel(tyche_batch_
             uint8_t *lits = area_lit(area, rec_cap) + b0;   // the part's own literals, in order (round 6)
             auto sink = [&](const uint2 *r, uint32_t n, uint32_t anchor) -> bool {
                 uint32_t ls, ll, ml, off;
-                lzp::decode_record(r, n, anchor, lane, ls, ll, ml, off, TYCHE_SINK_BACK ? in : nullptr);
+                lzp::decode_record(r, n, anchor, lane, ls, ll, ml, off, in);
                 if (nseq + n > slice) return false;
                 lown += copy_runs(in, ls, ll, lits + lown, lane, cmap);
                 if (lane < n) {
@@ -1676,25 +1664,16 @@ __device__ __forceinline__ void lct_encode(LaneBits &b, uint32_t &st, const uint
     st = X[(uint32_t)((int32_t)(st >> nbo) + (int32_t)(pk >> 19) - 128)];
 }
 
-// Pass B's LDS slot per lane.  TYCHE_ZSTD_FSE_SLOT 1 (default): only what the alphabets use --
+// Pass B's LDS slot per lane: only what the alphabets use --
 // 36 LL, 32 OF and 53 ML symbol words, each table's log after its words, then 128 / 64 / 128
 // state bytes (OF log <= 6): 816 bytes, 3 workgroups per CU instead of 2 at the full 1,152.
-#ifndef TYCHE_ZSTD_FSE_SLOT
-#define TYCHE_ZSTD_FSE_SLOT 1
-#endif
 struct FseSlot {
     uint32_t sll, sof, sml, xll, xof, xml, lll, lof, lml, words;   // word offsets in the slot
 };
-constexpr FseSlot kFseSlot = TYCHE_ZSTD_FSE_SLOT ? FseSlot{0, 37, 70, 124, 156, 172, 36, 69, 123, 204}
-                                                 : FseSlot{0, kCtWords, 2 * kCtWords, 64, kCtWords + 64,
-                                                           2 * kCtWords + 64, 63, kCtWords + 63, 2 * kCtWords + 63,
-                                                           3 * kCtWords};
+constexpr FseSlot kFseSlot = {0, 37, 70, 124, 156, 172, 36, 69, 123, 204};
 static_assert(kFseSlot.words % 4u == 0, "slot of 16-byte pieces");
 
-#ifndef TYCHE_ZSTD_FSE_PF
-#define TYCHE_ZSTD_FSE_PF 8
-#endif
-constexpr uint32_t kFsePf = TYCHE_ZSTD_FSE_PF;   // sequence records in flight per lane (pass B)
+constexpr uint32_t kFsePf = 8;   // sequence records in flight per lane (pass B)
 // ZSTD_compressSequences' bitstream (zstd_compress.c:695-735) for n >= 1
 // sequences; the same steps as emit_block's wave-uniform loop.  Returns its size.
 __device__ uint32_t fse_lane(uint8_t *out, const uint2 *Rg, const SeqMap m, uint32_t first, uint32_t n, const uint32_t *T) {
@@ -1770,19 +1749,15 @@ __global__ __launch_bounds__(64) void zstd_fse_kernel(tyche_batch_t b, size_t fi
         uint32_t *B = area_blk(area, k);
         if (!(B[7] & 2u)) continue;
         const uint32_t *g = area_tab(area, B[6]);
-        if (TYCHE_ZSTD_FSE_SLOT) {
-            for (uint32_t w = 0; w < 36u; w++) lt[kFseSlot.sll + w] = g[w];
-            for (uint32_t w = 0; w < 32u; w++) lt[kFseSlot.sof + w] = g[kCtWords + w];
-            for (uint32_t w = 0; w < 53u; w++) lt[kFseSlot.sml + w] = g[2u * kCtWords + w];
-            lt[kFseSlot.lll] = g[63];
-            lt[kFseSlot.lof] = g[kCtWords + 63u];
-            lt[kFseSlot.lml] = g[2u * kCtWords + 63u];
-            for (uint32_t w = 0; w < 32u; w++) lt[kFseSlot.xll + w] = g[64u + w];
-            for (uint32_t w = 0; w < 16u; w++) lt[kFseSlot.xof + w] = g[kCtWords + 64u + w];
-            for (uint32_t w = 0; w < 32u; w++) lt[kFseSlot.xml + w] = g[2u * kCtWords + 64u + w];
-        } else {
-            for (uint32_t w = 0; w < 3u * kCtWords / 4u; w++) ((u32x4 *)lt)[w] = ((const u32x4 *)g)[w];
-        }
+        for (uint32_t w = 0; w < 36u; w++) lt[kFseSlot.sll + w] = g[w];
+        for (uint32_t w = 0; w < 32u; w++) lt[kFseSlot.sof + w] = g[kCtWords + w];
+        for (uint32_t w = 0; w < 53u; w++) lt[kFseSlot.sml + w] = g[2u * kCtWords + w];
+        lt[kFseSlot.lll] = g[63];
+        lt[kFseSlot.lof] = g[kCtWords + 63u];
+        lt[kFseSlot.lml] = g[2u * kCtWords + 63u];
+        for (uint32_t w = 0; w < 32u; w++) lt[kFseSlot.xll + w] = g[64u + w];
+        for (uint32_t w = 0; w < 16u; w++) lt[kFseSlot.xof + w] = g[kCtWords + 64u + w];
+        for (uint32_t w = 0; w < 32u; w++) lt[kFseSlot.xml + w] = g[2u * kCtWords + 64u + w];
         B[3] = fse_lane(dst + B[0] + 3u + B[2], (const uint2 *)area_rec(area), seq_map(area, false), B[5], B[4], lt);
     }
 }
@@ -2067,14 +2042,14 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
 
 // The dictionary parse's table as a page finds it (zstd_parse_dict_kernel): kZWays = 2 positions
 // per bucket of the dictionary tail's n = D & ~63 bytes, keyed as parse_page keys its own inserts
-// (bucket_of<2> of TYCHE_HASH_BYTES = 5 bytes), for every position whose five bytes lie inside the
+// (bucket_of<2> of lzp::kHashBytes = 5 bytes), for every position whose five bytes lie inside the
 // tail.  Way 0 (tried first) is the bucket's latest position, as the parse would leave it; way 1
 // its earliest instead of its second latest: a long dictionary puts 8 to 17 positions into a
 // bucket, and with the two latest kept, nothing in its first three quarters could ever be found.
 // An empty way is position 0, as in a zeroed table (a candidate is verified by its bytes).
 size_t zstd_dict_seed_bytes() { return kTableSlots * sizeof(uint16_t); }
 void zstd_dict_seed_table(const uint8_t *tail, uint32_t n, void *table_out) {
-    static_assert(kZWays == 2 && TYCHE_HASH_BYTES == 5, "the seeded table is hashed for parse_page<true, false, 2>");
+    static_assert(kZWays == 2 && lzp::kHashBytes == 5, "the seeded table is hashed for parse_page<true, false, 2>");
     constexpr uint32_t nb = kTableSlots / 2u;
     uint32_t *T = (uint32_t *)table_out;
     std::fill(T, T + nb, 0u);

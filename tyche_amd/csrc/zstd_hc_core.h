@@ -6,7 +6,7 @@
 // compare the sequences of the kernel's frames with it.
 //
 // It writes no bytes: it fills the 64 lz_parse.h records (x = pos | cand << 16,
-// y = len; the backward extension is the sink's, TYCHE_SINK_BACK) and hands them
+// y = len; the backward extension is the sink's, lz_parse.h kSinkBack) and hands them
 // to sink(rec, n, anchor) in stream order exactly as lzp::parse_page does, and
 // returns the anchor of the last literal run, or 0xFFFFFFFF when the sink aborts.
 //
@@ -23,7 +23,7 @@
 //     highbit32(offset + 1); a repeat candidate has offset cost 0 and kRepBonus on
 //     top (its offset code has no extra bits and the cheapest symbols).  At the
 //     offsets of a page, 2^8..2^15, that lets a repeat candidate win when 3 to 5
-//     bytes shorter -- lz_parse.h's TYCHE_REP_SLACK of 3 at a near offset.
+//     bytes shorter -- lz_parse.h's kRepSlack of 3 at a near offset.
 //     Of equal gains the repeat candidates win, then the lower lane, then the ways.
 //   * the lazy rule on gains: position p stays a literal when gain(p + 1) >
 //     gain(p) + 4 or gain(p + 2) > gain(p) + 7 (the reference's depth 1 and 2);
