@@ -30,6 +30,11 @@ pages (up to 9 % on pages of fixed-size items) at 4-11x the default encoder's
 time, restored by ``decompress_pages`` in the same time as any other frame.
 ``dictionary=`` calls are as without the knob, and the two knobs are
 independent.
+zlib too: with ``TYCHE_ZLIB_HC=1`` or ``_lib.set_knob("ZLIB_HC", 1)`` every zlib
+compress call takes the high-compression parse -- ordinary zlib streams, 6-10 %
+fewer bytes on the bench pages (a quarter on pages of index-like items) at
+3-6x the default encoder's time, restored by ``decompress_pages`` in the time
+any other stream takes.  The three knobs are independent.
 
 Packed store: ``pack_pages`` appends the streams of ``compress_pages`` to a 1-D
 arena at their compressed size (``tyche_pack_batch``) and returns offsets and

@@ -163,6 +163,11 @@ hipError_t launch_zstd_encode(const tyche_batch_t &b, uint32_t in_cap, hipStream
 // zstd_hc_core.h; in_cap <= 65535).  launch_zstd_encode goes here when the knob is set.
 hipError_t launch_zstd_encode_hc(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_deflate(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
+// ZLIB_HC=1: the same stream format from a better parse -- 2^9 bucket rings of the 16 latest positions, the
+// nearest lower lane, the candidate of the highest gain (length against the distance's extra bits) and a
+// two-step lazy rule on gains (zlib_deflate_hc_kernel, zlib_hc_core.h; in_cap <= 65535) in front of the
+// default encoder's tree and code passes.  launch_zlib_deflate goes here when the knob is set.
+hipError_t launch_zlib_deflate_hc(const tyche_batch_t &b, uint32_t in_cap, hipStream_t s);
 hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStream_t s);
 hipError_t launch_zstd_decode(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, hipStream_t s);
 // zstd with a shared raw-content dictionary (zstd_encode.hip, zstd_decode.hip): dictionary + page is
