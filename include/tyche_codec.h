@@ -304,9 +304,10 @@ uint64_t tyche_pack_plan(size_t n, const int32_t *results, uint32_t max_length, 
  * Without a dictionary (tyche_lz4_use_dict never called or given NULL, no
  * TYCHE_LZ4_DICT, and the plain tyche_*_batch calls) nothing changes: the kernels
  * launched, the bytes and the results are the same.  LZ4_EXACT=1 and a dictionary
- * do not combine: a compress call that has both is TYCHE_E_BAD_ARGS.  zlib
- * ignores all of this; zstd has calls and a process-wide slot of its own for the
- * same handle ("zstd with a shared dictionary" below), which nothing here touches.
+ * do not combine: a compress call that has both is TYCHE_E_BAD_ARGS.  zstd and
+ * zlib each have calls and a process-wide slot of their own for the same handle
+ * ("zstd with a shared dictionary", "zlib with a shared dictionary" below), which
+ * nothing here touches.
  *
  * TYCHE_LZ4_DICT=<file> in the environment: the file's bytes become the
  * process-wide dictionary at the first LZ4 host-path call.  A file that is
@@ -398,6 +399,56 @@ int tyche_zstd_decompress_batch_dict(const tyche_dict_t *d, const tyche_batch_t 
 int tyche_zstd_use_dict(const tyche_dict_t *d);
 /* a new reference to the process-wide zstd dictionary (tyche_lz4_dict_destroy drops it), or NULL */
 tyche_dict_t *tyche_zstd_current_dict(void);
+
+/* ---- zlib with a shared dictionary ---------------------------------------- */
+/* The same handle again, as a zlib preset dictionary: what the reference's zlib 1.2.8 does with the
+ * bytes is the contract (deflateSetDictionary / inflateSetDictionary).  The reach rule, the lifetime
+ * rules and the per-page behaviour of the host entry points are those of the zstd section above, with
+ * tyche_zlib_use_dict, TYCHE_ZLIB_DICT and "zlib" in the reach text; what differs:
+ *
+ * Every handle is accepted: raw bytes are raw bytes to zlib, also those that begin with zstd's magic.
+ *
+ * The stream.  Header 78 3F, then DICTID, the adler32 of all D dictionary bytes, big-endian (what
+ * deflate.c writes at level 1 once a dictionary is set); then the default encoder's one final block,
+ * dynamic or fixed, whichever is smaller; then the adler32 of the page alone.  A distance may be at
+ * most min(32768, position + D).  The encoder matches against the dictionary's last D & ~63 bytes; the
+ * decoder honours all D.  Every coded stream carries FDICT and DICTID, also when no match reaches the
+ * dictionary.  The stored form is the one exception: with a DICTID it would be L + 15 bytes, above
+ * tyche_compress_bound for pages below 8192 bytes (zlib itself overruns compressBound there), so a page
+ * whose coded stream -- its 4 DICTID bytes counted -- would not be smaller than the stored form gets
+ * the plain encoder's stored stream, 78 01 and stored blocks, byte for byte: no DICTID, no dictionary
+ * match, restored by every zlib decoder with or without a dictionary.  So a stream is never longer
+ * than tyche_compress_bound and a capacity of exactly the bound never gives 0.  An empty page is not
+ * stored: it gets the default's empty block behind the dictionary header (12 bytes).  Compress results
+ * are the default zlib encoder's: the size, or 0 when the stream does not fit the capacity; nothing
+ * outside the slot is written; INT32_MIN above the launch's declared maximum, the slot left alone;
+ * the bytes depend on the page and the dictionary alone.
+ *
+ * Decode verdicts are uncompress's with the dictionary offered when inflate asks for it: inflateInit,
+ * inflate(Z_FINISH); on Z_NEED_DICT inflateSetDictionary (a failure is Z_DATA_ERROR) and
+ * inflate(Z_FINISH) again; then uncompr.c's mapping -- the decoded length, -3 or -5.  So a plain
+ * stream (no FDICT) decodes as ever and may not reach the dictionary (inflate never asked for it);
+ * any valid FLG with FDICT and the right DICTID decodes; a DICTID that is not this dictionary's
+ * adler32, or a stream that ends inside it, is -3; a distance of position + D is legal and one more
+ * is -3.  A wrong dictionary is therefore an error, never wrong bytes -- which neither LZ4 nor zstd
+ * can say.  The plain decoders keep giving -3 for an FDICT stream.  INT32_MIN only above the
+ * launch's dst_capacity (no stream maximum is used, as for plain zlib inflate).
+ *
+ * ZLIB_HC=1 loses where a dictionary reaches: tyche_zlib_compress_batch_dict ignores the knob, and
+ * with a process-wide dictionary the pages in reach take the dictionary encoder, the others HC.
+ * One serial one-wave kernel decodes every batch size.  The slot is zlib's own: the
+ * LZ4 and zstd calls and variables do not touch it, nor it theirs; without a zlib dictionary nothing
+ * changes.
+ *
+ * TYCHE_ZLIB_DICT=<file>: as TYCHE_ZSTD_DICT -- read once at the first zlib host-path call; a file
+ * that is unreadable, empty or longer than TYCHE_LZ4_DICT_MAX makes every zlib host call fail with
+ * TYCHE_E_BAD_ARGS and the reason; never silently ignored; tyche_zlib_use_dict replaces it. */
+int tyche_zlib_compress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream);
+int tyche_zlib_decompress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream);
+/* process-wide zlib dictionary of the host entry points; NULL removes it.  Holds a reference of its own. */
+int tyche_zlib_use_dict(const tyche_dict_t *d);
+/* a new reference to the process-wide zlib dictionary (tyche_lz4_dict_destroy drops it), or NULL */
+tyche_dict_t *tyche_zlib_current_dict(void);
 
 /* ---- training a dictionary from sample pages ------------------------------ */
 /* The trainer picks the 128-byte segments of the sample pages whose 8-byte keys occur in the most

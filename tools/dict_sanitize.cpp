@@ -12,9 +12,9 @@
 //   ./dict_sanitize          -> "dict_sanitize ok", exit 0, no sanitizer report
 //
 // What it does: create / retain (the slots, tyche_*_current_dict) / release; install, replace and
-// remove in both slots from two threads at once; tyche_lz4_dict_bytes; and, in a fresh child process
-// each (the variables are read once per process), TYCHE_LZ4_DICT and TYCHE_ZSTD_DICT naming an empty,
-// an over-long and a good file.
+// remove in all three slots (LZ4, zstd, zlib) from two threads at once; tyche_lz4_dict_bytes; and, in a
+// fresh child process each (the variables are read once per process), TYCHE_LZ4_DICT, TYCHE_ZSTD_DICT
+// and TYCHE_ZLIB_DICT naming an empty, an over-long and a good file.
 #include <spawn.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,6 +38,17 @@ extern char **environ;
         }                                                                              \
     } while (0)
 
+// the three slots: the codec of each, its variable, its install and its read call
+struct Slot {
+    int codec;
+    const char *var;
+    int (*use)(const tyche_dict_t *);
+    tyche_dict_t *(*current)(void);
+};
+static const Slot kSlots[3] = {{TYCHE_LZ4_COMPRESSOR_ID, "TYCHE_LZ4_DICT", tyche_lz4_use_dict, tyche_lz4_current_dict},
+                               {TYCHE_ZSTD_COMPRESSOR_ID, "TYCHE_ZSTD_DICT", tyche_zstd_use_dict, tyche_zstd_current_dict},
+                               {TYCHE_ZLIB_COMPRESSOR_ID, "TYCHE_ZLIB_DICT", tyche_zlib_use_dict, tyche_zlib_current_dict}};
+
 static int host_compress(int codec) {
     uint8_t page[100] = {0}, out[800];
     const void *src = page;
@@ -50,28 +61,33 @@ static int host_compress(int codec) {
 // child: the variable `var` (already in the environment) names a file; `want` is the error text it
 // must give ("" for a file that serves, of `len` bytes)
 static int env_child(const char *var, const char *want, uint32_t len) {
-    const bool lz4 = strcmp(var, "TYCHE_LZ4_DICT") == 0;
-    const int own = lz4 ? TYCHE_LZ4_COMPRESSOR_ID : TYCHE_ZSTD_COMPRESSOR_ID;
-    const int other = lz4 ? TYCHE_ZSTD_COMPRESSOR_ID : TYCHE_LZ4_COMPRESSOR_ID;
-    tyche_lz4_dict_t *cur = lz4 ? tyche_lz4_current_dict() : tyche_zstd_current_dict();
-    CHECK(!(lz4 ? tyche_zstd_current_dict() : tyche_lz4_current_dict()));   // the other slot reads nothing
-    const int rc = host_compress(own);
+    const Slot *own = nullptr;
+    for (const Slot &s : kSlots)
+        if (strcmp(var, s.var) == 0) own = &s;
+    CHECK(own);
+    tyche_lz4_dict_t *cur = own->current();
+    for (const Slot &s : kSlots)
+        if (&s != own) CHECK(!s.current());   // the other slots read nothing
+    const int rc = host_compress(own->codec);
     if (*want) {
         CHECK(!cur && rc == TYCHE_E_BAD_ARGS);
         CHECK(strstr(tyche_last_error(), var) && strstr(tyche_last_error(), want));
     } else {
         CHECK(cur && tyche_lz4_dict_length(cur) == len && rc != TYCHE_E_BAD_ARGS);
         tyche_lz4_dict_destroy(cur);
-        CHECK((lz4 ? tyche_lz4_use_dict(NULL) : tyche_zstd_use_dict(NULL)) == TYCHE_E_OK);   // the slot's reference goes
+        CHECK(own->use(NULL) == TYCHE_E_OK);   // the slot's reference goes
     }
-    CHECK(host_compress(other) != TYCHE_E_BAD_ARGS);
+    for (const Slot &s : kSlots)
+        if (&s != own) CHECK(host_compress(s.codec) != TYCHE_E_BAD_ARGS);
     return 0;
 }
 
 static void run_env_child(const char *var, const std::string &path, const char *want, uint32_t len) {
     std::vector<std::string> env;
     for (char **e = environ; *e; e++)
-        if (strncmp(*e, "TYCHE_LZ4_DICT", 14) != 0 && strncmp(*e, "TYCHE_ZSTD_DICT", 15) != 0) env.push_back(*e);
+        if (strncmp(*e, "TYCHE_LZ4_DICT", 14) != 0 && strncmp(*e, "TYCHE_ZSTD_DICT", 15) != 0 &&
+            strncmp(*e, "TYCHE_ZLIB_DICT", 15) != 0)
+            env.push_back(*e);
     env.push_back(std::string(var) + "=" + path);
     std::vector<char *> envp;
     for (auto &e : env) envp.push_back(&e[0]);
@@ -106,7 +122,7 @@ int main(int argc, char **argv) {
     write_file(empty, 0);
     write_file(big, TYCHE_LZ4_DICT_MAX + 1u);
     write_file(good, 4096);
-    for (const char *var : {"TYCHE_LZ4_DICT", "TYCHE_ZSTD_DICT"}) {
+    for (const char *var : {"TYCHE_LZ4_DICT", "TYCHE_ZSTD_DICT", "TYCHE_ZLIB_DICT"}) {
         run_env_child(var, empty, "is empty", 0);
         run_env_child(var, big, "longer than", 0);
         run_env_child(var, good, "", 4096);
@@ -130,35 +146,35 @@ int main(int argc, char **argv) {
     CHECK(tyche_lz4_dict_bytes(NULL, blob.data(), 4) == 0 && tyche_lz4_dict_length(NULL) == 0);
     tyche_lz4_dict_destroy(NULL);
 
-    // two threads install, replace, read and remove in both slots; each drops its creator's reference
+    // two threads install, replace, read and remove in all three slots; each drops its creator's reference
     // while the slot may still hold the handle
     auto worker = [&](uint32_t seed) {
         for (uint32_t k = 0; k < 2000; k++) {
             const uint32_t len = 64u + (seed * 977u + k * 31u) % 2048u;
             tyche_lz4_dict_t *d = tyche_lz4_dict_create(blob.data() + (k & 255u), len);
             CHECK(d);
-            CHECK(((k + seed) & 1u ? tyche_lz4_use_dict(d) : tyche_zstd_use_dict(d)) == TYCHE_E_OK);
+            CHECK(kSlots[(k + seed) % 3u].use(d) == TYCHE_E_OK);
             tyche_lz4_dict_destroy(d);
-            for (tyche_lz4_dict_t *cur : {tyche_lz4_current_dict(), tyche_zstd_current_dict()})
+            for (tyche_lz4_dict_t *cur : {tyche_lz4_current_dict(), tyche_zstd_current_dict(), tyche_zlib_current_dict()})
                 if (cur) {
                     uint8_t head[16];
                     CHECK(tyche_lz4_dict_bytes(cur, head, sizeof(head)) == tyche_lz4_dict_length(cur));
                     tyche_lz4_dict_destroy(cur);
                 }
-            if (k % 7u == 0) CHECK((k & 1u ? tyche_lz4_use_dict(NULL) : tyche_zstd_use_dict(NULL)) == TYCHE_E_OK);
-            if (k % 97u == 0) (void)host_compress(seed & 1u ? TYCHE_LZ4_COMPRESSOR_ID : TYCHE_ZSTD_COMPRESSOR_ID);
+            if (k % 7u == 0) CHECK(kSlots[k % 3u].use(NULL) == TYCHE_E_OK);
+            if (k % 97u == 0) (void)host_compress(kSlots[(k + seed) % 3u].codec);
         }
     };
     std::thread a(worker, 1u), b(worker, 2u);
     a.join();
     b.join();
-    CHECK(tyche_lz4_use_dict(NULL) == TYCHE_E_OK && tyche_zstd_use_dict(NULL) == TYCHE_E_OK);
-    CHECK(!tyche_lz4_current_dict() && !tyche_zstd_current_dict());
+    for (const Slot &s : kSlots) CHECK(s.use(NULL) == TYCHE_E_OK && !s.current());
 
-    // a structured dictionary: zstd's slot refuses it, LZ4's takes it
+    // a structured dictionary: zstd's slot refuses it, LZ4's and zlib's take it
     const uint8_t magic[8] = {0x37, 0xA4, 0x30, 0xEC, 1, 2, 3, 4};
     tyche_lz4_dict_t *m = tyche_lz4_dict_create(magic, sizeof(magic));
     CHECK(m && tyche_zstd_use_dict(m) == TYCHE_E_BAD_ARGS && tyche_lz4_use_dict(m) == TYCHE_E_OK);
+    CHECK(tyche_zlib_use_dict(m) == TYCHE_E_OK && tyche_zlib_use_dict(NULL) == TYCHE_E_OK);
     CHECK(tyche_lz4_use_dict(NULL) == TYCHE_E_OK);
     tyche_lz4_dict_destroy(m);
     puts("dict_sanitize ok");

@@ -14,14 +14,14 @@ from ._lib import (COMPRESSOR_IDS, E_BAD_ARGS, E_BUFFER_ALREADY_COMPRESSED, E_BU
 
 
 def __getattr__(name):
-    # Dictionary (the shared-dictionary handle, for LZ4 and zstd) and use_zstd_dict live in
+    # Dictionary (the shared-dictionary handle, for all three codecs), use_zstd_dict and use_zlib_dict live in
     # tyche_amd.codec, which needs torch: resolved on first use, so importing the package does not
-    if name in ("Dictionary", "Lz4Dict", "use_zstd_dict"):
+    if name in ("Dictionary", "Lz4Dict", "use_zstd_dict", "use_zlib_dict"):
         from . import codec
         return getattr(codec, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
-__all__ = ["Dictionary", "Lz4Dict", "use_zstd_dict", "COMPRESSOR_IDS", "E_BAD_ARGS", "E_BUFFER_ALREADY_COMPRESSED", "E_BUFFER_ALREADY_DECOMPRESSED",
+__all__ = ["Dictionary", "Lz4Dict", "use_zstd_dict", "use_zlib_dict", "COMPRESSOR_IDS", "E_BAD_ARGS", "E_BUFFER_ALREADY_COMPRESSED", "E_BUFFER_ALREADY_DECOMPRESSED",
            "E_BUFFER_COMPRESSION_PROBLEM", "E_BUFFER_MISSING_DATA", "E_BUFFER_NOT_FOUND", "E_DEVICE", "E_OK",
            "LZ4_COMPRESSOR_ID", "NO_COMPRESSOR_ID", "ZLIB_COMPRESSOR_ID", "ZSTD_COMPRESSOR_ID", "load"]

@@ -146,6 +146,10 @@ SIGNATURES = {
     "tyche_zstd_decompress_batch_dict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Batch), ctypes.c_void_p]),
     "tyche_zstd_use_dict": (ctypes.c_int, [ctypes.c_void_p]),
     "tyche_zstd_current_dict": (ctypes.c_void_p, []),
+    "tyche_zlib_compress_batch_dict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Batch), ctypes.c_void_p]),
+    "tyche_zlib_decompress_batch_dict": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Batch), ctypes.c_void_p]),
+    "tyche_zlib_use_dict": (ctypes.c_int, [ctypes.c_void_p]),
+    "tyche_zlib_current_dict": (ctypes.c_void_p, []),
     "tyche_lz4_dict_train_batch": (ctypes.c_void_p, [ctypes.POINTER(Batch), ctypes.c_uint32, ctypes.c_void_p]),
     "tyche_lz4_dict_train_host": (ctypes.c_void_p, [ctypes.c_size_t, _vpp, _u32p, ctypes.c_uint32]),
     "tyche_compress_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_size_t, _vpp, _u32p, _vpp, _u32p,

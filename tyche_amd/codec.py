@@ -42,18 +42,22 @@ lengths, ``decompress_packed`` decodes from them, ``compress_pages_packed`` does
 compress + append a chunk of rows at a time.  A store's state is two int64 words
 on the device, ``{used, wanted}``; the device decides whether an append fits.
 
-Shared dictionary (LZ4 and zstd): ``dictionary=Dictionary(bytes)`` makes the
+Shared dictionary (all three codecs): ``dictionary=Dictionary(bytes)`` makes the
 dictionary and each row one window.  LZ4: the blocks are what
 ``LZ4_decompress_safe_usingDict`` restores.  zstd: the bytes are a raw-content
 dictionary, the frames what ``ZSTD_decompress_usingDict`` restores (bytes that
 begin with zstd's dictionary magic 37 A4 30 EC are refused: structured
 dictionaries are not supported).  Either way the same dictionary is needed to
 decode, and row length (capacity, when decoding) plus dictionary may not exceed
-65,536 bytes.  zlib has no dictionary (``ValueError``).  ``Dictionary`` is the
-codec-neutral name of ``Lz4Dict``: one handle serves both codecs.
+65,536 bytes.  zlib: the bytes are a preset dictionary, the streams what
+``inflateSetDictionary`` + ``inflate`` restore (header 78 3F and the dictionary's
+adler32; a row that does not compress is the plain stored stream), so a wrong
+dictionary is an error (-3), never wrong bytes.  ``Dictionary`` is the
+codec-neutral name of ``Lz4Dict``: one handle serves all three codecs.
 ``Lz4Dict.train(pages, length)`` makes one from sample pages on the GPU;
 ``Lz4Dict.data`` returns a dictionary's bytes.  ``use_zstd_dict(d)`` installs
-one for the host entry points' zstd calls (``None`` removes it).
+one for the host entry points' zstd calls (``None`` removes it),
+``use_zlib_dict(d)`` one for their zlib calls; the three slots are independent.
 """
 from __future__ import annotations
 
@@ -62,7 +66,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import LZ4_COMPRESSOR_ID, ZSTD_COMPRESSOR_ID
+from ._lib import LZ4_COMPRESSOR_ID, ZLIB_COMPRESSOR_ID, ZSTD_COMPRESSOR_ID
 
 SLOT_ALIGN = 128
 
@@ -93,7 +97,7 @@ def _check_pages(t: torch.Tensor, name: str) -> None:
 
 class Lz4Dict:
     """A shared dictionary (tyche_lz4_dict_create): 1..LZ4_DICT_MAX bytes, copied, immutable, for the
-    LZ4 and the zstd calls alike (``Dictionary`` is the same class).  The engine uploads it to a
+    LZ4, zstd and zlib calls alike (``Dictionary`` is the same class).  The engine uploads it to a
     device the first time a launch there uses it."""
 
     def __init__(self, data: bytes):
@@ -169,6 +173,22 @@ def use_zstd_dict(dictionary: Lz4Dict | None) -> None:
                "tyche_zstd_use_dict")
 
 
+def use_zlib_dict(dictionary: Lz4Dict | None) -> None:
+    """Installs ``dictionary`` as the process-wide zlib dictionary of the host entry points
+    (tyche_zlib_use_dict); ``None`` removes it.  The LZ4 and zstd slots are not touched."""
+    _lib.check(_lib.load().tyche_zlib_use_dict(dictionary.handle if dictionary is not None else None),
+               "tyche_zlib_use_dict")
+
+
+def _zlib_dict_call(compress: bool, compressor_id: int, b, stream: int, dictionary) -> bool:
+    """zlib and a dictionary: the tyche_zlib_*_batch_dict call; False when the call is not that."""
+    if dictionary is None or compressor_id != ZLIB_COMPRESSOR_ID:
+        return False
+    name = "tyche_zlib_compress_batch_dict" if compress else "tyche_zlib_decompress_batch_dict"
+    _lib.check(getattr(_lib.load(), name)(dictionary.handle, ctypes.byref(b), stream), name)
+    return True
+
+
 def _compress_call(compressor_id: int, level: int, b, stream: int, dictionary) -> None:
     if dictionary is None:
         _lib.check(_lib.load().tyche_compress_batch(compressor_id, level, ctypes.byref(b), stream), "tyche_compress_batch")
@@ -216,7 +236,8 @@ def compress_pages(pages: torch.Tensor, compressor_id: int = LZ4_COMPRESSOR_ID, 
     _check_pages(out, "out")
     b = _lib.Batch(count=n, src=_ptr(pages), src_stride=page_len, src_length=page_len, max_src_length=page_len,
                    dst=_ptr(out), dst_stride=out.shape[1], dst_capacity=out.shape[1], results=_ptr(out_len))
-    _compress_call(compressor_id, level, b, _stream_handle(pages.device), dictionary)
+    if not _zlib_dict_call(True, compressor_id, b, _stream_handle(pages.device), dictionary):
+        _compress_call(compressor_id, level, b, _stream_handle(pages.device), dictionary)
     return out, out_len
 
 
@@ -242,7 +263,8 @@ def decompress_pages(slots: torch.Tensor, comp_len: torch.Tensor, page_len: int,
     b = _lib.Batch(count=n, src=_ptr(slots), src_lengths=_ptr(comp_len), src_stride=slots.shape[1],
                    max_src_length=min(cap, slots.shape[1]), dst=_ptr(out), dst_stride=out.shape[1],
                    dst_capacity=page_len, results=_ptr(rv))
-    _decompress_call(compressor_id, b, _stream_handle(slots.device), dictionary)
+    if not _zlib_dict_call(False, compressor_id, b, _stream_handle(slots.device), dictionary):
+        _decompress_call(compressor_id, b, _stream_handle(slots.device), dictionary)
     return out, rv
 
 
@@ -253,7 +275,8 @@ def decompress_ragged(stream: torch.Tensor, offsets: torch.Tensor, lengths: torc
     b = _lib.Batch(count=offsets.numel(), src=_ptr(stream), src_offsets=_ptr(offsets), src_lengths=_ptr(lengths),
                    max_src_length=max_src_length, dst=_ptr(out), dst_offsets=_ptr(out_offsets),
                    dst_capacities=_ptr(capacities), dst_capacity=max_capacity, results=_ptr(rv))
-    _decompress_call(compressor_id, b, _stream_handle(stream.device), dictionary)
+    if not _zlib_dict_call(False, compressor_id, b, _stream_handle(stream.device), dictionary):
+        _decompress_call(compressor_id, b, _stream_handle(stream.device), dictionary)
     return out, rv
 
 
@@ -266,7 +289,8 @@ def compress_ragged(src: torch.Tensor, offsets: torch.Tensor, lengths: torch.Ten
     b = _lib.Batch(count=offsets.numel(), src=_ptr(src), src_offsets=_ptr(offsets), src_lengths=_ptr(lengths),
                    max_src_length=max_src_length, dst=_ptr(out), dst_offsets=_ptr(out_offsets),
                    dst_capacities=_ptr(capacities), results=_ptr(results))
-    _compress_call(compressor_id, level, b, _stream_handle(src.device), dictionary)
+    if not _zlib_dict_call(True, compressor_id, b, _stream_handle(src.device), dictionary):
+        _compress_call(compressor_id, level, b, _stream_handle(src.device), dictionary)
     return out, results
 
 
@@ -341,7 +365,8 @@ def decompress_packed(arena: torch.Tensor, offsets: torch.Tensor, lengths: torch
     b = _lib.Batch(count=n, src=_ptr(arena), src_offsets=_ptr(offsets), src_lengths=_ptr(lengths),
                    max_src_length=max_comp_len, dst=_ptr(out), dst_stride=out.shape[1], dst_capacity=page_len,
                    results=_ptr(rv))
-    _decompress_call(compressor_id, b, _stream_handle(arena.device), dictionary)
+    if not _zlib_dict_call(False, compressor_id, b, _stream_handle(arena.device), dictionary):
+        _decompress_call(compressor_id, b, _stream_handle(arena.device), dictionary)
     return out, rv
 
 

@@ -9,8 +9,8 @@
 
 namespace tyche {
 
-// What differs between the codecs that take a dictionary (dict.hip): one constant each, LZ4's for
-// TYCHE_LZ4_COMPRESSOR_ID and zstd's for TYCHE_ZSTD_COMPRESSOR_ID (the ids that may be asked for).
+// What differs between the codecs (dict.hip): one constant for each of TYCHE_LZ4_COMPRESSOR_ID,
+// TYCHE_ZSTD_COMPRESSOR_ID and TYCHE_ZLIB_COMPRESSOR_ID (the ids that may be asked for).
 struct DictCodec;
 const DictCodec &dict_codec(int compressor_id);
 
@@ -29,7 +29,7 @@ struct DictHold {
 struct DictUploadNote {
     std::mutex mu;
     std::string msg;
-    hipError_t upload(const tyche_lz4_dict_t *d, Lz4DictDev *img, const void **seed);   // seed NULL: the image alone
+    hipError_t upload(const tyche_lz4_dict_t *d, Lz4DictDev *img, const void **seed, int which);   // seed NULL: the image alone; which: DictCodec::seed
     int finish(int rc);
 };
 

@@ -1,5 +1,5 @@
 // dict.hip -- the shared-dictionary layer of libtyche_codec.so: the handle and its device copies, the
-// process-wide slot of each codec that takes a dictionary (LZ4, zstd) with its environment variable,
+// process-wide slot of each codec (LZ4, zstd, zlib) with its environment variable,
 // TYCHE_LZ4_DICT_AUTO, the training glue, the reach rule of the host path (dict.h) and every
 // extern "C" dictionary symbol of include/tyche_codec.h.  Host code only; the kernels it launches are
 // engine.h's.
@@ -51,16 +51,19 @@ struct DevBlob {
 struct tyche_lz4_dict {
     std::atomic<long> refs{1};
     uint32_t len = 0, dpad = 0, enc_len = 0, enc_stride = 0;
+    uint32_t adler = 1;   // adler32 of the bytes: zlib's DICTID
     std::mutex mu;
     DevBlob image;   // dec (dpad) | table (8 KiB) | enc (16 x enc_stride)
-    // the zstd encoder's seeded table (engine.h: zstd_dict_seed_table), built at the handle's first zstd
-    // compress and uploaded to a device at its first one there: LZ4-only users pay nothing for it
-    DevBlob zseed;
+    // the zstd and the zlib encoder's seeded tables (engine.h: zstd_dict_seed_table, zlib_dict_seed_table;
+    // DictCodec::seed - 1 indexes them), each built at the handle's first compress of that codec and
+    // uploaded to a device at its first one there: users of other codecs pay nothing for it
+    DevBlob seeds[2];
     const uint8_t *bytes() const { return image.host.data() + (dpad - len); }
 };
 
 namespace {
-constexpr int kLz4 = TYCHE_LZ4_COMPRESSOR_ID, kZstd = TYCHE_ZSTD_COMPRESSOR_ID;   // for dict_codec
+constexpr int kLz4 = TYCHE_LZ4_COMPRESSOR_ID, kZstd = TYCHE_ZSTD_COMPRESSOR_ID, kZlib = TYCHE_ZLIB_COMPRESSOR_ID;   // for dict_codec
+enum { kSeedNone = 0, kSeedZstd = 1, kSeedZlib = 2 };   // DictCodec::seed
 constexpr size_t kDictTableBytes = 4096 * sizeof(uint16_t);
 // the encoder's table key (lz_parse.h's hash5 at TYCHE_HASH_LOG 12, lz4_encode_dict.hip): 5 bytes
 inline uint32_t dict_hash(const uint8_t *p) {
@@ -75,15 +78,16 @@ void dict_release(const tyche_lz4_dict *cd) {
     if (!d || d->refs.fetch_sub(1) != 1) return;
     DeviceGuard keep;
     for (int i = 0; i < kMaxDevices; i++)
-        if ((d->image.dev[i] || d->zseed.dev[i]) && hipSetDevice(i) == hipSuccess)
-            for (DevBlob *b : {&d->image, &d->zseed})
+        if ((d->image.dev[i] || d->seeds[0].dev[i] || d->seeds[1].dev[i]) && hipSetDevice(i) == hipSuccess)
+            for (DevBlob *b : {&d->image, &d->seeds[0], &d->seeds[1]})
                 if (b->dev[i]) (void)hipFree(b->dev[i]);
     delete d;
 }
 
-// The handle's image on the current device and, where `seed` is asked for, the zstd encoder's seeded
-// table there, each uploaded on first use.  A failure is returned and named in the thread's error text.
-hipError_t dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, const void **seed) {
+// The handle's image on the current device and, where `seed` is asked for, the seeded table of kind
+// `which` (kSeedZstd, kSeedZlib) there, each uploaded on first use.  A failure is returned and named
+// in the thread's error text.
+hipError_t dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, const void **seed, int which) {
     tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
     int dev = -1;
     hipError_t e = hipGetDevice(&dev);
@@ -99,12 +103,16 @@ hipError_t dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, const void 
     out->dpad = d->dpad;
     out->enc_len = d->enc_len;
     out->enc_stride = d->enc_stride;
-    if (!seed) return hipSuccess;
-    if (d->zseed.host.empty()) {
-        d->zseed.host.resize(zstd_dict_seed_bytes());
-        zstd_dict_seed_table(d->image.host.data() + (d->dpad - d->enc_len), d->enc_len, d->zseed.host.data());
+    out->adler = d->adler;
+    if (!seed || which == kSeedNone) return hipSuccess;
+    DevBlob &sb = d->seeds[which - 1];
+    if (sb.host.empty()) {
+        const uint8_t *tail = d->image.host.data() + (d->dpad - d->enc_len);
+        sb.host.resize(which == kSeedZlib ? zlib_dict_seed_bytes() : zstd_dict_seed_bytes());
+        if (which == kSeedZlib) zlib_dict_seed_table(tail, d->enc_len, sb.host.data());
+        else zstd_dict_seed_table(tail, d->enc_len, sb.host.data());
     }
-    if ((e = d->zseed.on(dev, "dictionary table", &p)) != hipSuccess) return e;
+    if ((e = sb.on(dev, "dictionary table", &p)) != hipSuccess) return e;
     *seed = p;
     return hipSuccess;
 }
@@ -124,6 +132,12 @@ tyche_lz4_dict *dict_create(const void *bytes, uint32_t len) {
     std::vector<uint8_t> &image = d->image.host;
     image.assign((size_t)d->dpad + kDictTableBytes + 16u * (size_t)d->enc_stride, 0);
     memcpy(image.data() + (d->dpad - len), src, len);
+    uint32_t a = 1, b = 0;   // adler32.c:65
+    for (uint32_t j = 0; j < len; j++) {
+        a = (a + src[j]) % 65521u;
+        b = (b + a) % 65521u;
+    }
+    d->adler = (b << 16) | a;
     // every position of the encoder's part whose 5 hashed bytes lie inside it, the last of equal hashes kept
     // (window position j = byte j of the part); an empty slot is position 0, as in a zeroed table
     const uint8_t *tail = src + (len - d->enc_len);
@@ -157,11 +171,13 @@ int lz4_precheck(const tyche_lz4_dict *, bool decode) {
     return !decode && knob("LZ4_EXACT", 0) != 0 ? dict_exact_conflict() : TYCHE_E_OK;
 }
 int zstd_precheck(const tyche_lz4_dict *d, bool) { return zdict_structured(d) ? zdict_structured_error() : TYCHE_E_OK; }
+int zlib_precheck(const tyche_lz4_dict *, bool) { return TYCHE_E_OK; }   // raw bytes are raw bytes to zlib: every handle
 hipError_t lz4_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, const void *, bool per_page, hipStream_t s) {
     return launch_lz4_encode_dict(b, in_cap, d, per_page, s);
 }
 uint32_t lz4_stream_bound(uint32_t n) { return lz4_bound(n); }
 uint32_t zstd_stream_bound(uint32_t n) { return zstd_bound(n); }
+uint32_t zlib_stream_bound(uint32_t n) { return zlib_bound(n); }
 }  // namespace
 
 struct tyche::DictCodec {
@@ -170,16 +186,18 @@ struct tyche::DictCodec {
     bool (*refuses)(const tyche_lz4_dict *);                 // a handle this codec cannot take (NULL: takes every one)
     int (*precheck)(const tyche_lz4_dict *, bool decode);
     uint32_t (*bound)(uint32_t);
-    bool seed;                  // the encoder takes the handle's seeded table
+    int seed;                   // the seeded table of the handle's that the encoder takes (kSeedNone: none)
     hipError_t (*encode)(const tyche_batch_t &, uint32_t in_cap, const Lz4DictDev &, const void *seed, bool per_page, hipStream_t);
     hipError_t (*decode)(const tyche_batch_t &, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &, bool per_page, hipStream_t);
 };
 const DictCodec &tyche::dict_codec(int compressor_id) {
-    static const DictCodec codecs[2] = {
-        {"LZ4", "lz4", "TYCHE_LZ4_DICT", nullptr, lz4_precheck, lz4_stream_bound, false, lz4_encode_dict, launch_lz4_decode_dict},
-        {"zstd", "zstd", "TYCHE_ZSTD_DICT", zdict_structured, zstd_precheck, zstd_stream_bound, true, launch_zstd_encode_dict,
-         launch_zstd_decode_dict}};
-    return codecs[compressor_id == TYCHE_ZSTD_COMPRESSOR_ID];
+    static const DictCodec codecs[3] = {
+        {"LZ4", "lz4", "TYCHE_LZ4_DICT", nullptr, lz4_precheck, lz4_stream_bound, kSeedNone, lz4_encode_dict, launch_lz4_decode_dict},
+        {"zstd", "zstd", "TYCHE_ZSTD_DICT", zdict_structured, zstd_precheck, zstd_stream_bound, kSeedZstd, launch_zstd_encode_dict,
+         launch_zstd_decode_dict},
+        {"zlib", "zlib", "TYCHE_ZLIB_DICT", nullptr, zlib_precheck, zlib_stream_bound, kSeedZlib, launch_zlib_deflate_dict,
+         launch_zlib_inflate_dict}};
+    return codecs[compressor_id == kZstd ? 1 : compressor_id == kZlib ? 2 : 0];
 }
 
 namespace {
@@ -201,7 +219,7 @@ struct AutoTrain {
 };
 // The process-wide dictionary of a codec's host entry points.  Heap state that is never destroyed: a
 // restore dispatcher may still run a batch at exit().  Each codec has its own:
-// neither tyche_<codec>_use_dict nor the codec's variables touch the other's.
+// neither tyche_<codec>_use_dict nor the codec's variables touch another's.
 struct DictSlot {
     const DictCodec &c;
     AutoTrain *const autos;   // NULL: the codec has no auto mode
@@ -211,8 +229,9 @@ struct DictSlot {
     std::string env_error;   // the variable named a file that cannot serve: every host call of the codec fails with it
 };
 DictSlot &dict_slot(const DictCodec &c) {
-    static DictSlot &lz4 = *new DictSlot{dict_codec(kLz4), new AutoTrain}, &zstd = *new DictSlot{dict_codec(kZstd), nullptr};
-    return &c == &dict_codec(kLz4) ? lz4 : zstd;
+    static DictSlot &lz4 = *new DictSlot{dict_codec(kLz4), new AutoTrain}, &zstd = *new DictSlot{dict_codec(kZstd), nullptr},
+                    &zlib = *new DictSlot{dict_codec(kZlib), nullptr};
+    return &c == &dict_codec(kLz4) ? lz4 : &c == &dict_codec(kZstd) ? zstd : zlib;
 }
 // TYCHE_LZ4_DICT_AUTO=<bytes> [TYCHE_LZ4_DICT_AUTO_PAGES=<pages>] (slot locked): false when unset
 bool auto_env_locked(DictSlot &S, const char *path) {
@@ -300,7 +319,7 @@ int dict_reach_error(const DictCodec &c, bool decode, uint32_t cap, uint32_t dle
     return bad_args(std::string(c.name) + " dictionary reach: the launch's largest " + (decode ? "capacity" : "page") + " (" +
                     std::to_string(cap) + ") plus the dictionary (" + std::to_string(dlen) + " bytes) exceeds 65536");
 }
-// the four tyche_<codec>_<direction>_batch_dict calls
+// the six tyche_<codec>_<direction>_batch_dict calls
 int batch_dict(const DictCodec &c, bool decode, const tyche_lz4_dict *d, const tyche_batch_t *batch, hipStream_t s) {
     if (!d || !batch) return TYCHE_E_BAD_ARGS;
     if (int rc = c.precheck(d, decode)) return rc;
@@ -312,7 +331,7 @@ int batch_dict(const DictCodec &c, bool decode, const tyche_lz4_dict *d, const t
     if (int rc = stream_device(s)) return rc;
     Lz4DictDev img;
     const void *seed = nullptr;
-    if (dict_on_device(d, &img, !decode && c.seed ? &seed : nullptr) != hipSuccess) return TYCHE_E_DEVICE;
+    if (dict_on_device(d, &img, !decode && c.seed ? &seed : nullptr, c.seed) != hipSuccess) return TYCHE_E_DEVICE;
     hipError_t e;
     if (decode)
         // (a declared stream maximum is only a bound -- a slot width, say: above the longest stream a
@@ -339,8 +358,8 @@ int tyche::DictHold::get(const DictCodec &c) {
 }
 tyche::DictHold::~DictHold() { dict_release(d); }
 
-hipError_t tyche::DictUploadNote::upload(const tyche_lz4_dict *d, Lz4DictDev *img, const void **seed) {
-    const hipError_t why = dict_on_device(d, img, seed);
+hipError_t tyche::DictUploadNote::upload(const tyche_lz4_dict *d, Lz4DictDev *img, const void **seed, int which) {
+    const hipError_t why = dict_on_device(d, img, seed, which);
     if (why == hipSuccess) return why;
     std::lock_guard<std::mutex> g(mu);
     if (msg.empty()) msg = thread_error();
@@ -358,7 +377,7 @@ hipError_t tyche::dict_launch(const DictCodec &c, bool decode, const tyche_lz4_d
                               const tyche_batch_t &b, hipStream_t s, bool host_dst, LaunchRef plain) {
     Lz4DictDev img;
     const void *seed = nullptr;
-    if (const hipError_t ue = note.upload(d, &img, !decode && c.seed ? &seed : nullptr)) return ue;
+    if (const hipError_t ue = note.upload(d, &img, !decode && c.seed ? &seed : nullptr, c.seed)) return ue;
     const uint32_t reach = 65536u - d->len, longest = std::max(b.max_src_length, 1u);
     const uint32_t in_cap = decode ? std::min(b.max_src_length, c.bound(65536u)) : longest;   // (a stream bound, as batch_dict's)
     const uint32_t cap = decode ? b.dst_capacity : longest;
@@ -511,8 +530,10 @@ uint32_t tyche_lz4_dict_bytes(const tyche_lz4_dict_t *d, void *out, uint32_t cap
 
 int tyche_lz4_use_dict(const tyche_lz4_dict_t *d) { return dict_use(dict_codec(kLz4), d); }
 int tyche_zstd_use_dict(const tyche_dict_t *d) { return dict_use(dict_codec(kZstd), d); }
+int tyche_zlib_use_dict(const tyche_dict_t *d) { return dict_use(dict_codec(kZlib), d); }
 tyche_lz4_dict_t *tyche_lz4_current_dict(void) { return dict_current(dict_codec(kLz4)); }
 tyche_dict_t *tyche_zstd_current_dict(void) { return dict_current(dict_codec(kZstd)); }
+tyche_dict_t *tyche_zlib_current_dict(void) { return dict_current(dict_codec(kZlib)); }
 
 int tyche_lz4_compress_batch_dict(const tyche_lz4_dict_t *d, const tyche_batch_t *batch, void *stream) {
     return batch_dict(dict_codec(kLz4), false, d, batch, (hipStream_t)stream);
@@ -525,6 +546,13 @@ int tyche_zstd_compress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *b
 }
 int tyche_zstd_decompress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream) {
     return batch_dict(dict_codec(kZstd), true, d, batch, (hipStream_t)stream);
+}
+
+int tyche_zlib_compress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream) {
+    return batch_dict(dict_codec(kZlib), false, d, batch, (hipStream_t)stream);
+}
+int tyche_zlib_decompress_batch_dict(const tyche_dict_t *d, const tyche_batch_t *batch, void *stream) {
+    return batch_dict(dict_codec(kZlib), true, d, batch, (hipStream_t)stream);
 }
 
 tyche_lz4_dict_t *tyche_lz4_dict_train_batch(const tyche_batch_t *samples, uint32_t dict_len, void *stream) {

@@ -30,6 +30,8 @@ __host__ __device__ inline uint32_t lz4_bound(uint32_t n) {
 }
 // zstd 1.1.2 ZSTD_compressBound (zstd_compress.c:37): FSE_compressBound(n) + 12
 inline uint32_t zstd_bound(uint32_t n) { return n + (n >> 7) + 512u + 12u; }
+// zlib 1.2.8 compressBound (compress.c:74-78)
+inline uint32_t zlib_bound(uint32_t n) { return n + (n >> 12) + (n >> 14) + (n >> 25) + 13u; }
 
 // in_cap for a decode batch: the largest stream length (or a bound for unknown lengths)
 inline uint32_t decode_in_cap(const tyche_batch_t &b, uint32_t fallback) {
@@ -123,12 +125,13 @@ hipError_t launch_lz4_decode_large(const tyche_batch_t &b, uint32_t in_cap, uint
 // and device): `dec` is dpad bytes (a multiple of 16) with the dictionary's dlen bytes at their end;
 // `table` the 4,096 16-bit positions of the encoder's read-only dictionary table; `enc` 16 images
 // of enc_stride = enc_len + 16 bytes, image h holding the dictionary's last enc_len = dlen & ~63
-// bytes from byte h on (zeros around them).
+// bytes from byte h on (zeros around them).  `adler` is the adler32 of the dlen bytes, computed on
+// the host when the handle is made: zlib's DICTID.
 struct Lz4DictDev {
     const uint8_t *dec;
     const uint16_t *table;
     const uint8_t *enc;
-    uint32_t dlen, dpad, enc_len, enc_stride;
+    uint32_t dlen, dpad, enc_len, enc_stride, adler;
 };
 // LZ4 with a shared dictionary (lz4_encode_dict.hip, lz4_decode_dict.hip): dictionary + page is one
 // window of at most 65,536 bytes.  per_page: pages beyond that reach are skipped, their results
@@ -184,6 +187,19 @@ hipError_t launch_zstd_encode_dict(const tyche_batch_t &b, uint32_t in_cap, cons
                                    bool per_page, hipStream_t s);
 hipError_t launch_zstd_decode_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &d,
                                    bool per_page, hipStream_t s);
+// zlib with a shared dictionary (zlib_deflate_dict.hip; zlib_inflate.hip's zlib_inflate_dict_kernel):
+// dictionary + page is one window of at most 65,536 bytes, the stream what deflateSetDictionary /
+// inflateSetDictionary produce and take (header 78 3F and DICTID = d.adler; a page whose coded stream
+// would not beat the stored form is the plain stored stream).  The handle and its image are the LZ4
+// dictionary's; the encoder also takes a seeded table of its own, zlib_dict_seed_bytes() bytes that
+// zlib_dict_seed_table computes on the host from the dictionary's last d.enc_len bytes.  The decoder
+// is the serial one for every batch size and ignores in_cap.  per_page as for LZ4.
+size_t zlib_dict_seed_bytes();
+void zlib_dict_seed_table(const uint8_t *tail, uint32_t n, void *table_out);
+hipError_t launch_zlib_deflate_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, const void *seed,
+                                    bool per_page, hipStream_t s);
+hipError_t launch_zlib_inflate_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &d,
+                                    bool per_page, hipStream_t s);
 // Dynamic page assignment.  The codec kernels run one-wave workgroups that loop
 // over pages; when a CU holds a number of waves that is not a multiple of its 4
 // SIMDs, the waves sharing a SIMD run slower than the lone ones, and static

@@ -527,9 +527,6 @@ std::string codec_msg(int id) {
     return "unknown compressor id " + std::to_string(id);
 }
 
-// zlib 1.2.8 compressBound (compress.c:74-78)
-inline uint32_t zlib_bound(uint32_t n) { return n + (n >> 12) + (n >> 14) + (n >> 25) + 13u; }
-
 constexpr size_t kBulkSmallMax = 64;   // pages of up to 65,536 bytes a raw LZ4 host decode batch may hold beside larger ones
 
 }  // namespace
@@ -724,12 +721,11 @@ int tyche_compress_host(int compressor_id, int compressor_level, size_t n, const
     auto plain = [compressor_id](const tyche_batch_t &b, hipStream_t s, bool) {
         return launch_encode(compressor_id, b, std::max(b.max_src_length, 1u), s);
     };
-    // LZ4 and zstd with a process-wide dictionary (each codec's own): the reach rule, dict_launch
-    const DictCodec *dc = compressor_id != TYCHE_ZLIB_COMPRESSOR_ID ? &dict_codec(compressor_id) : nullptr;
+    // with a process-wide dictionary (each codec's own): the reach rule, dict_launch
+    const DictCodec *dc = &dict_codec(compressor_id);
     DictHold dict;
     AutoSample trained_from;   // TYCHE_LZ4_DICT_AUTO: the sample, when this call completed it
-    if (dc)
-        if (int rc = dict.get(*dc)) return rc;
+    if (int rc = dict.get(*dc)) return rc;
     if (compressor_id == TYCHE_LZ4_COMPRESSOR_ID)
         if (int rc = lz4_host_compress_rules(dict.d, n, src, src_lengths, &trained_from)) return rc;
     if (dict.d) {
@@ -749,19 +745,15 @@ int tyche_decompress_host(int compressor_id, size_t n, const void *const *src, c
                           void *const *dst, const uint32_t *dst_capacities, int32_t *results) {
     if (!valid_codec(compressor_id)) { t_error = codec_msg(compressor_id); return TYCHE_E_BAD_ARGS; }
     if (n == 0) return TYCHE_E_OK;
-    if (compressor_id == TYCHE_ZLIB_COMPRESSOR_ID)
-        return run_host(n, src, src_lengths, dst, dst_capacities, results,
-                              [](const tyche_batch_t &b, hipStream_t s, bool) {
-                                  return launch_zlib_inflate(b, b.dst_capacity, s);
-                              }, true);
-    // LZ4 and zstd with a process-wide dictionary (each codec's own): the reach rule, dict_launch
+    // with a process-wide dictionary (each codec's own): the reach rule, dict_launch
     const DictCodec &dc = dict_codec(compressor_id);
     DictHold dict;
     DictUploadNote note;
     if (int rc = dict.get(dc)) return rc;
-    if (compressor_id == TYCHE_ZSTD_COMPRESSOR_ID) {
-        auto plain = [](const tyche_batch_t &b, hipStream_t s, bool) {
-            return launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
+    if (compressor_id != TYCHE_LZ4_COMPRESSOR_ID) {
+        const bool zlib = compressor_id == TYCHE_ZLIB_COMPRESSOR_ID;
+        auto plain = [zlib](const tyche_batch_t &b, hipStream_t s, bool) {
+            return zlib ? launch_zlib_inflate(b, b.dst_capacity, s) : launch_zstd_decode(b, b.max_src_length, b.dst_capacity, s);
         };
         return note.finish(run_host(n, src, src_lengths, dst, dst_capacities, results,
                                     [&](const tyche_batch_t &b, hipStream_t s, bool host_dst) {

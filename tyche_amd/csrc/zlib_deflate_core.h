@@ -28,10 +28,11 @@
 // first, <= 31 bits), a DPP prefix sum gives bit offsets, the bits are OR-ed
 // into a 128-dword LDS staging area, and complete bytes go to HBM.
 //
-// This header holds the device code both kernels share: zlib_deflate.hip is the
-// default encoder (encode_page<false>, the shared greedy parse as pass 1) and
+// This header holds the device code the kernels share: zlib_deflate.hip is the
+// default encoder (encode_page<false>, the shared greedy parse as pass 1),
 // zlib_deflate_hc.hip the high-compression one (encode_page<true>, ZLIB_HC=1,
-// which alone sees zlib_hc_core.h).
+// which alone sees zlib_hc_core.h) and zlib_deflate_dict.hip the one with a shared
+// dictionary (encode_page<false, true>).
 // Each is a translation unit of its own, so that adding the second kernel leaves
 // the first one's inlining, registers and code as they were.
 #pragma once
@@ -264,24 +265,43 @@ __device__ int32_t emit_stored(const uint8_t *in, uint32_t L, uint8_t *dst, uint
     return (int32_t)(op + 4);
 }
 
+// The zlib header of a coded stream: 78 01, or with a preset dictionary (kDict) 78 3F and DICTID,
+// the adler32 of the dictionary, big-endian (deflate.c:781-815 at level 1 once a dictionary is set).
+// Returns the header's bytes.  The stored form is always the plain one (emit_stored).
+template <bool kDict>
+__device__ __forceinline__ uint32_t put_zlib_head(uint8_t *dst, uint32_t dictid, uint32_t lane) {
+    if constexpr (kDict) {
+        if (lane == 0) { dst[0] = 0x78; dst[1] = 0x3F; }
+        if (lane < 4) dst[2u + lane] = (uint8_t)(dictid >> (24u - 8u * lane));
+        return 6u;
+    } else {
+        if (lane == 0) { dst[0] = 0x78; dst[1] = 0x01; }
+        return 2u;
+    }
+}
+
 // One pass with the fixed codes (the parse codes as it goes).  Returns the
-// stream size, or 0 if even the stored form does not fit in cap.
+// stream size, or 0 if even the stored form does not fit in cap.  kDict: the header
+// carries dictid; the parse is the page's own (no match reaches the dictionary).
+template <bool kDict = false>
 __device__ int32_t encode_fixed1(const uint8_t *in, uint32_t L, uint32_t adler, uint16_t *table, uint8_t *map,
-                                 uint2 *rec, uint32_t *stage, uint8_t *dst, uint32_t cap, uint32_t lane) {
+                                 uint2 *rec, uint32_t *stage, uint8_t *dst, uint32_t cap, uint32_t lane,
+                                 uint32_t dictid = 0) {
+    constexpr uint32_t kHead = kDict ? 6u : 2u;
     for (uint32_t w = lane; w < kTableSlots / 8; w += kWave) ((u32x4 *)table)[w] = u32x4{0, 0, 0, 0};
     WAVE_SYNC();
     const uint32_t nblk = L ? (L + 65534u) / 65535u : 1u;
     const uint32_t stored = 2u + L + 5u * nblk + 4u;
     Out o;
     o.dst = dst;
-    o.op = 2;
+    o.op = kHead;
     o.limit = min(stored, cap);           // the fixed-code stream must beat the stored form
     o.stage = stage;
     o.nbits = 3;                          // BFINAL = 1, BTYPE = 01
     for (uint32_t w = lane; w < kStageWords; w += kWave) stage[w] = w == 0 ? 3u : 0u;
     __builtin_amdgcn_wave_barrier();
-    bool ok = 2u < o.limit;
-    if (ok && lane == 0) { dst[0] = 0x78; dst[1] = 0x01; }
+    bool ok = kHead < o.limit;
+    if (ok) put_zlib_head<kDict>(dst, dictid, lane);
     uint32_t anchor = 0;
     if (ok) {
         auto sink = [&](const uint2 *r, uint32_t n, uint32_t anc) -> bool {
@@ -368,10 +388,19 @@ __device__ __attribute__((unused)) uint2 hc_pass1(const uint8_t *in, uint32_t L,
 // high-compression parse (hc_pass1; table is then its rings, of which passes 2
 // and 3 and the fixed-code fallback use the first kTableSlots slots, and cnt
 // its ring counters right behind them), else the shared greedy parse.
-template <bool kHc>
+// kDict (zlib_deflate_dict.hip): the DE bytes in front of `in` are a dictionary's tail (DE a multiple
+// of 64) and `table` holds its positions already; pass 1 parses the window [in - DE, in + L) from
+// position DE, and its records are turned into page positions before they are stored, so passes 2 and
+// 3 are the plain ones: they read literals at page positions and take a distance as a number, never
+// compared with a position.  The header carries dictid, and its 4 bytes count in the size choice; a
+// page whose coded stream would not be smaller than the stored form gets the plain stored stream
+// (no FDICT: every inflate restores it), an empty page the empty coded stream behind the header.
+template <bool kHc, bool kDict = false>
 __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, uint8_t *map, uint2 *rec,
                                uint32_t *stage, uint8_t *dst, uint32_t cap, uint8_t *ws, uint32_t ws_bytes,
-                               uint32_t lane, uint8_t *cnt = nullptr) {
+                               uint32_t lane, uint8_t *cnt = nullptr, uint32_t DE = 0, uint32_t dictid = 0) {
+    static_assert(!(kHc && kDict), "the dictionary encoder's pass 1 is the greedy parse");
+    constexpr uint32_t kHead = kDict ? 6u : 2u;
     const uint32_t adler = lds_adler32(in, L, lane);
     const uint32_t nblk = L ? (L + 65534u) / 65535u : 1u;
     const uint32_t stored = 2u + L + 5u * nblk + 4u;
@@ -391,21 +420,29 @@ __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, u
         anchor = r.x;
         nrec = r.y;
     } else {
-        for (uint32_t w = lane; w < kTableSlots / 8; w += kWave) ((u32x4 *)table)[w] = u32x4{0, 0, 0, 0};
-        WAVE_SYNC();
+        if constexpr (!kDict) {
+            for (uint32_t w = lane; w < kTableSlots / 8; w += kWave) ((u32x4 *)table)[w] = u32x4{0, 0, 0, 0};
+            WAVE_SYNC();
+        }
         auto sink = [&](const uint2 *r, uint32_t n, uint32_t anc) -> bool {
             if (nrec + n > room) return false;
             uint32_t ls, ll, ml, off;
             lzp::decode_record(r, n, anc, lane, ls, ll, ml, off);
+            if constexpr (kDict) ls -= DE;                       // window position -> page position (anc >= DE)
             if (off > 32768u) { ll += ml; ml = 0; off = 1; }     // beyond the deflate window: literals
             if (lane < n) recs[-1 - (int32_t)(nrec + lane)] = make_uint2(ls | (ll << 16), ml | (off << 16));
             nrec += n;
             return true;
         };
-        anchor = lzp::parse_page<kRep, kMin3, kWays>(in, L, table, rec, lane, sink);
+        if constexpr (kDict) {
+            anchor = lzp::parse_page<kRep, kMin3, kWays>(in - DE, DE + L, table, rec, lane, sink, DE);
+            if (anchor != 0xFFFFFFFFu) anchor -= DE;
+        } else {
+            anchor = lzp::parse_page<kRep, kMin3, kWays>(in, L, table, rec, lane, sink);
+        }
     }
     if (anchor == 0xFFFFFFFFu || nrec + 1u > room)
-        return encode_fixed1(in, L, adler, table, map, rec, stage, dst, cap, lane);
+        return encode_fixed1<kDict>(in, L, adler, table, map, rec, stage, dst, cap, lane, dictid);
     if (lane == 0) recs[-1 - (int32_t)nrec] = make_uint2(anchor | ((L - anchor) << 16), 1u << 16);   // last literals
     nrec += 1;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");   // records visible, L1 invalidated
@@ -501,9 +538,10 @@ __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, u
     const bool dyn = dyn_bits < fixed_bits;
     // ---- size checks: below the stored form, below the records still to be read
     const uint32_t bits = dyn ? dyn_bits : fixed_bits;
-    const uint32_t size = 2u + (bits + 7u) / 8u + 4u;
+    const uint32_t size = kHead + (bits + 7u) / 8u + 4u;
     const uint32_t rec_lo = own ? cap : (uint32_t)(top - base) - 8u * nrec;
-    if (size >= stored || size > cap) return emit_stored(in, L, dst, cap, adler, lane);
+    if (kDict && L == 0u && size > cap) return 0;   // (the empty page has one stream: no stored form steps in below its size)
+    if ((size >= stored && !(kDict && L == 0u)) || size > cap) return emit_stored(in, L, dst, cap, adler, lane);
     // (the stream may not reach records still to be read: checked as it grows, o.limit)
     // ---- codes (bit-reversed | length << 16) over the histograms
     uint32_t rll[5], rd[1], rcl[1];
@@ -521,19 +559,19 @@ __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, u
     // ---- pass 3: header and symbols
     Out o;
     o.dst = dst;
-    o.op = 2;
+    o.op = kHead;
     o.limit = min(rec_lo, cap);
     o.stage = stage;
     o.nbits = 0;
     for (uint32_t w = lane; w < kStageWords; w += kWave) stage[w] = 0;
     __builtin_amdgcn_wave_barrier();
-    if (lane == 0) { dst[0] = 0x78; dst[1] = 0x01; }
+    put_zlib_head<kDict>(dst, dictid, lane);
     if (dyn) {
         put_uniform(o, 1u | (2u << 1), 3, lane);                       // BFINAL, BTYPE 10
         put_uniform(o, (nlit - 257u) | ((ndist - 1u) << 5) | ((ncl - 4u) << 10), 14, lane);
         for (uint32_t i = 0; i < ncl; i++) put_uniform(o, rdlane(lcl[0], c_cl_order[i]), 3, lane);
         __builtin_amdgcn_wave_barrier();
-        if (!drain(o, lane)) return encode_fixed1(in, L, adler, table, map, rec, stage, dst, cap, lane);
+        if (!drain(o, lane)) return encode_fixed1<kDict>(in, L, adler, table, map, rec, stage, dst, cap, lane, dictid);
         auto emit_cl = [&](uint32_t sym, uint32_t x, uint32_t nxb) {
             put_uniform(o, rdlane(rcl[0], sym), rdlane(lcl[0], sym), lane);
             put_uniform(o, x, nxb, lane);
@@ -589,7 +627,7 @@ __device__ int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, u
         __builtin_amdgcn_wave_barrier();
         ok = drain(o, lane) && o.op + 4u <= o.limit;
     }
-    if (!ok) return encode_fixed1(in, L, adler, table, map, rec, stage, dst, cap, lane);
+    if (!ok) return encode_fixed1<kDict>(in, L, adler, table, map, rec, stage, dst, cap, lane, dictid);
     if (lane < 4) dst[o.op + lane] = (uint8_t)(adler >> (24u - 8u * lane));
     return (int32_t)(o.op + 4u);
 }

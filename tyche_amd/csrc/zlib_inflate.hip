@@ -370,15 +370,37 @@ __device__ __forceinline__ uint32_t cl_order(uint32_t i) {
     return (uint32_t)((i < 12 ? lo >> (5 * i) : hi >> (5 * (i - 12))) & 31u);
 }
 
-// zlib header (RFC 1950: CMF/FLG, inflate.c HEAD); 0 or kZData
-__device__ __forceinline__ int32_t zlib_header(BitReader &r, uint32_t lane) {
+// What a decoder with a shared dictionary knows of it (zlib_inflate_dict_kernel): its length and its
+// adler32; an empty type for the plain instantiations, as zstd's DictReach<kDict> is.
+template <bool kDict>
+struct ZDict {};
+template <>
+struct ZDict<true> {
+    uint32_t dlen, id;
+};
+
+// zlib header (RFC 1950: CMF/FLG, inflate.c HEAD); 0 or kZData.  FDICT: the plain decoders have no
+// dictionary to offer (Z_NEED_DICT is uncompress's Z_DATA_ERROR); the dictionary decoder reads DICTID
+// (inflate.c DICTID), whose mismatch is inflateSetDictionary's Z_DATA_ERROR, and sets *reach to the
+// dictionary's length -- a stream without FDICT never asks for the dictionary, so its reach stays 0.
+template <bool kDict = false>
+__device__ __forceinline__ int32_t zlib_header(BitReader &r, uint32_t lane, ZDict<kDict> zd = {}, int32_t *reach = nullptr) {
     refill(r, lane);
     if (r.avail < 16) return kZData;
     const uint32_t cmf = take(r, 8), flg = take(r, 8);
     if (((cmf << 8) | flg) % 31u) return kZData;
     if ((cmf & 15u) != 8u) return kZData;
     if ((cmf >> 4) + 8u > 15u) return kZData;
-    if (flg & 0x20u) return kZData;
+    if constexpr (kDict) {
+        if (flg & 0x20u) {
+            refill(r, lane);
+            if (r.avail < 32) return kZData;
+            if (__builtin_bswap32(take(r, 32)) != zd.id) return kZData;
+            *reach = (int32_t)zd.dlen;
+        }
+    } else {
+        if (flg & 0x20u) return kZData;
+    }
     return 0;
 }
 
@@ -450,9 +472,16 @@ __device__ __forceinline__ int32_t block_head(BitReader &r, uint32_t &last, Tabl
 
 // Decodes one zlib stream into out (LDS, cap bytes).  Returns the decoded
 // length or kZData / kZBuf, as oracle_zlib_uncompress.
+// kDict: the zd.dlen bytes in front of out are the dictionary; a stream that asks for it (FDICT) may
+// copy from up to that far before the page, and a pending match's source is then a negative index --
+// flush_matches computes sources as signed numbers, packs only the destination (a page position, below
+// 65,536) and the distance (at most 32,768) into 16 bits each, and the dictionary never changes, so a
+// match that begins in it, overlaps its own output or runs over the seam is the copy it always was.
+template <bool kDict = false>
 __device__ __forceinline__ int32_t inflate_page(BitReader &r, const uint8_t *src, uint8_t *out, int32_t cap, uint8_t *lens,
-                                uint16_t *sortL, uint16_t *sortD, uint32_t lane) {
-    if (zlib_header(r, lane)) return kZData;
+                                uint16_t *sortL, uint16_t *sortD, uint32_t lane, ZDict<kDict> zd = {}) {
+    int32_t reach = 0;   // bytes before the page a distance may reach
+    if (zlib_header<kDict>(r, lane, zd, &reach)) return kZData;
     Table L, D;
     Pending q;
     q.lit = q.md = q.mx = 0;
@@ -507,7 +536,7 @@ __device__ __forceinline__ int32_t inflate_page(BitReader &r, const uint8_t *src
             x = e_extra(e);
             if ((int32_t)x > r.avail) return kZData;
             const uint32_t dist = e_val(e) + take(r, x);
-            if ((int32_t)dist > op) return kZData;
+            if ((int32_t)dist > (kDict ? op + reach : op)) return kZData;
             if (op + (int32_t)len > cap) return kZBuf;
             q.md = put_lane(q.md, q.nmat, (uint32_t)op, lane);
             q.mx = put_lane(q.mx, q.nmat, dist | (len << 16), lane);
@@ -1032,6 +1061,45 @@ __global__ __launch_bounds__(64) void zlib_inflate_kernel(tyche_batch_t b, uint3
     }
 }
 
+// The serial decoder with a shared dictionary (tyche_zlib_decompress_batch_dict, and the host entry
+// points once a process-wide zlib dictionary is installed), for every batch size.  LDS: the handle's
+// decoder image (Lz4DictDev::dec: D rounded up to 16, the bytes right-aligned), staged once per
+// workgroup, directly in front of the output window of zlib_inflate_kernel.
+// per_page: the host entry points' reach rule -- a page with capacity + D > 65536 is not this kernel's
+// (its result is left alone: another launch over the same batch owns it).
+__global__ __launch_bounds__(64) void zlib_inflate_dict_kernel(tyche_batch_t b, uint32_t out_cap, uint32_t off_lens,
+                                                               Lz4DictDev d, uint32_t per_page, unsigned *ctr) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const uint32_t lane = threadIdx.x;
+    uint8_t *out = smem + d.dpad;
+    uint8_t *lens = out + off_lens;
+    uint16_t *sortL = (uint16_t *)(lens + 320);
+    uint16_t *sortD = sortL + 320;
+    for (uint32_t v = lane; v < (d.dpad >> 4); v += kWave) ((u32x4 *)smem)[v] = ((const u32x4 *)d.dec)[v];
+    WAVE_SYNC();
+    ZDict<true> zd;
+    zd.dlen = d.dlen;
+    zd.id = d.adler;
+    for (size_t page = blockIdx.x; page < b.count; page = ctr ? claim_page(ctr, lane) : page + gridDim.x) {
+        const PageRef p = batch_page(b, page);
+        if (per_page && (uint64_t)p.dst_cap + d.dlen > 65536u) continue;
+        int32_t rv;
+        if (p.dst_cap > out_cap || p.src_len > 0x0FFFFFFFu) {
+            rv = kResultTooLarge;
+        } else {
+            BitReader r;
+            reader_init(r, p, lane);
+            r.wa = load_win(r, 0, lane);
+            r.wb = load_win(r, 256, lane);
+            rv = inflate_page<true>(r, p.src, out, (int32_t)p.dst_cap, lens, sortL, sortD, lane, zd);
+            WAVE_SYNC();
+            if (rv > 0) stage_out(p.dst, out, (uint32_t)rv, lane, kWave);
+        }
+        if (lane == 0) b.results[page] = rv;
+        WAVE_SYNC();
+    }
+}
+
 // The latency kernel: inflate_par per page (stream staged in LDS), the serial
 // decoder when it falls back.  LDS: output window | lens/sorted | LT | DT | M |
 // stage.
@@ -1333,6 +1401,24 @@ hipError_t launch_zlib_inflate(const tyche_batch_t &b, uint32_t out_cap, hipStre
     if (!ctr.get()) return hipErrorOutOfMemory;
     hipLaunchKernelGGL(zlib_inflate_kernel, dim3((unsigned)grid), dim3(kWave), lds, s, b, out_cap, off_lens,
                        ctr.get());
+    return hipGetLastError();
+}
+
+// One kernel for every batch size: the lane-parallel and jump kernels return kFallback on a distance
+// beyond the output, which is what a dictionary match is to them.  in_cap is not used, as the plain
+// launch uses no stream maximum.  per_page: pages beyond the reach are skipped; else out_cap + D must
+// not exceed 65,536.
+hipError_t launch_zlib_inflate_dict(const tyche_batch_t &b, uint32_t, uint32_t out_cap, const Lz4DictDev &d, bool per_page,
+                                    hipStream_t s) {
+    if (b.count == 0) return hipSuccess;
+    if ((uint64_t)out_cap + d.dlen > 65536u || d.dlen > d.dpad || (d.dpad & 15u)) return hipErrorInvalidValue;
+    const uint32_t off_lens = (out_cap + 64u + 15u) & ~15u;
+    const size_t lds = (size_t)d.dpad + off_lens + 320 + 2 * 320 + 2 * 32;
+    const size_t grid = page_grid((const void *)zlib_inflate_dict_kernel, kWave, lds, b.count);
+    WorkCounter ctr(s, grid < b.count);
+    if (!ctr.get()) return hipErrorOutOfMemory;
+    hipLaunchKernelGGL(zlib_inflate_dict_kernel, dim3((unsigned)grid), dim3(kWave), lds, s, b, out_cap, off_lens, d,
+                       per_page ? 1u : 0u, grid < b.count ? ctr.get() : nullptr);
     return hipGetLastError();
 }
 
