@@ -605,6 +605,29 @@ size_t tyche_plan_split(size_t n, const uint32_t *src_lengths, int ndev, uint64_
  * never the decode result.  compressor_level stays ignored.  LZ4 and zstd ignore
  * the knob, zlib ignores LZ4_HC and ZSTD_HC; ZLIB_HC_PAGES_PER_CU caps the
  * resident pages per CU (an occupancy A/B, 0: what fits).
+ * An eighth, LZ4_HC_DICT (default 0), independent of LZ4_HC, sends every LZ4
+ * page that a dictionary reaches (length + dictionary <= 65536) to the
+ * high-compression dictionary encoder: tyche_lz4_compress_batch_dict, and with
+ * a process-wide dictionary (tyche_lz4_use_dict, TYCHE_LZ4_DICT, or one
+ * installed by TYCHE_LZ4_DICT_AUTO) tyche_compress_host, buffer__compress,
+ * tyche_buffers_compress and every device of the multi-device fan-out.  It is
+ * LZ4_HC's parse over the dictionary encoder's window (8 ring candidates per
+ * position, the rings seeded from the dictionary once per handle, a two-step
+ * lazy choice), and the contract is the dictionary encoder's, as under "LZ4
+ * with a shared dictionary": a standard block whose offsets may reach into the
+ * dictionary, restored by tyche_lz4_decompress_batch_dict and
+ * LZ4_decompress_safe_usingDict with the same dictionary; results[i] the size,
+ * or 0 when the stream does not fit dst_capacity; nothing at or past dst +
+ * dst_capacity written; src_len == 0 gives 0x00; INT32_MIN above the launch's
+ * maximum; no stream longer than tyche_compress_bound; the bytes depend on the
+ * page and the dictionary alone.  Pages outside the reach, and every page
+ * while TYCHE_LZ4_DICT_AUTO collects its sample, are as without the knob:
+ * LZ4_HC alone decides their encoder.  Without a dictionary the knob does
+ * nothing; with the knob at 0, LZ4_HC=1 beside a dictionary is as above.  It
+ * never makes a launch fail, and LZ4_EXACT=1 with a dictionary stays
+ * TYCHE_E_BAD_ARGS.  zstd and zlib ignore the knob.
+ * LZ4_HC_DICT_PAGES_PER_CU caps the resident pages per CU (an occupancy A/B,
+ * 0: what fits).
  * Two are test hooks: FAIL_COMPRESS_EVERY=N fails every Nth compress launch
  * (TYCHE_E_DEVICE, the device-failure test) and LOG_ERRORS=1 prints engine
  * errors to stderr. */

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "..", "build", "tyche_amd")
 LIB = os.path.join(HERE, "libtyche_codec.so")
-SOURCES = ["engine.hip", "lz4_decode.hip", "lz4_decode_lane.hip", "lz4_decode_lc.hip", "lz4_encode.hip", "lz4_encode_exact.hip", "lz4_encode_hc.hip", "lz4_encode_large.hip", "lz4_decode_large.hip", "lz4_encode_dict.hip", "lz4_decode_dict.hip", "lz4_dict_train.hip", "zlib_inflate.hip", "zstd_decode.hip", "zstd_encode.hip", "zlib_deflate.hip", "zlib_deflate_hc.hip", "zlib_deflate_dict.hip", "pagegen.hip", "pack.hip", "page_order.hip", "host_batch.hip", "dict.hip",
+SOURCES = ["engine.hip", "lz4_decode.hip", "lz4_decode_lane.hip", "lz4_decode_lc.hip", "lz4_encode.hip", "lz4_encode_exact.hip", "lz4_encode_hc.hip", "lz4_encode_large.hip", "lz4_decode_large.hip", "lz4_encode_dict.hip", "lz4_encode_hc_dict.hip", "lz4_hc_dict_seed.hip", "lz4_decode_dict.hip", "lz4_dict_train.hip", "zlib_inflate.hip", "zstd_decode.hip", "zstd_encode.hip", "zlib_deflate.hip", "zlib_deflate_hc.hip", "zlib_deflate_dict.hip", "pagegen.hip", "pack.hip", "page_order.hip", "host_batch.hip", "dict.hip",
            "errno_guard.hip"]   # errno_guard last: its constructor runs after the code-object registrations
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"

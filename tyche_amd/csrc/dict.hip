@@ -54,16 +54,17 @@ struct tyche_lz4_dict {
     uint32_t adler = 1;   // adler32 of the bytes: zlib's DICTID
     std::mutex mu;
     DevBlob image;   // dec (dpad) | table (8 KiB) | enc (16 x enc_stride)
-    // the zstd and the zlib encoder's seeded tables (engine.h: zstd_dict_seed_table, zlib_dict_seed_table;
-    // DictCodec::seed - 1 indexes them), each built at the handle's first compress of that codec and
-    // uploaded to a device at its first one there: users of other codecs pay nothing for it
-    DevBlob seeds[2];
+    // the zstd and the zlib encoder's seeded tables and the LZ4_HC_DICT encoder's seeded rings (engine.h:
+    // zstd_dict_seed_table, zlib_dict_seed_table, lz4_hc_dict_seed_table; the seed kind - 1 indexes them),
+    // each built at the handle's first compress of that kind and uploaded to a device at its first one
+    // there: users of other codecs and modes pay nothing for it
+    DevBlob seeds[3];
     const uint8_t *bytes() const { return image.host.data() + (dpad - len); }
 };
 
 namespace {
 constexpr int kLz4 = TYCHE_LZ4_COMPRESSOR_ID, kZstd = TYCHE_ZSTD_COMPRESSOR_ID, kZlib = TYCHE_ZLIB_COMPRESSOR_ID;   // for dict_codec
-enum { kSeedNone = 0, kSeedZstd = 1, kSeedZlib = 2 };   // DictCodec::seed
+enum { kSeedNone = 0, kSeedZstd = 1, kSeedZlib = 2, kSeedLz4Hc = 3 };   // DictCodec::seed; encode_seed
 constexpr size_t kDictTableBytes = 4096 * sizeof(uint16_t);
 // the encoder's table key (lz_parse.h's hash5 at TYCHE_HASH_LOG 12, lz4_encode_dict.hip): 5 bytes
 inline uint32_t dict_hash(const uint8_t *p) {
@@ -78,14 +79,14 @@ void dict_release(const tyche_lz4_dict *cd) {
     if (!d || d->refs.fetch_sub(1) != 1) return;
     DeviceGuard keep;
     for (int i = 0; i < kMaxDevices; i++)
-        if ((d->image.dev[i] || d->seeds[0].dev[i] || d->seeds[1].dev[i]) && hipSetDevice(i) == hipSuccess)
-            for (DevBlob *b : {&d->image, &d->seeds[0], &d->seeds[1]})
+        if ((d->image.dev[i] || d->seeds[0].dev[i] || d->seeds[1].dev[i] || d->seeds[2].dev[i]) && hipSetDevice(i) == hipSuccess)
+            for (DevBlob *b : {&d->image, &d->seeds[0], &d->seeds[1], &d->seeds[2]})
                 if (b->dev[i]) (void)hipFree(b->dev[i]);
     delete d;
 }
 
 // The handle's image on the current device and, where `seed` is asked for, the seeded table of kind
-// `which` (kSeedZstd, kSeedZlib) there, each uploaded on first use.  A failure is returned and named
+// `which` (kSeedZstd, kSeedZlib, kSeedLz4Hc) there, each uploaded on first use.  A failure is returned and named
 // in the thread's error text.
 hipError_t dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, const void **seed, int which) {
     tyche_lz4_dict *d = const_cast<tyche_lz4_dict *>(cd);
@@ -108,8 +109,9 @@ hipError_t dict_on_device(const tyche_lz4_dict *cd, Lz4DictDev *out, const void 
     DevBlob &sb = d->seeds[which - 1];
     if (sb.host.empty()) {
         const uint8_t *tail = d->image.host.data() + (d->dpad - d->enc_len);
-        sb.host.resize(which == kSeedZlib ? zlib_dict_seed_bytes() : zstd_dict_seed_bytes());
+        sb.host.resize(which == kSeedZlib ? zlib_dict_seed_bytes() : which == kSeedLz4Hc ? lz4_hc_dict_seed_bytes() : zstd_dict_seed_bytes());
         if (which == kSeedZlib) zlib_dict_seed_table(tail, d->enc_len, sb.host.data());
+        else if (which == kSeedLz4Hc) lz4_hc_dict_seed_table(tail, d->enc_len, sb.host.data());
         else zstd_dict_seed_table(tail, d->enc_len, sb.host.data());
     }
     if ((e = sb.on(dev, "dictionary table", &p)) != hipSuccess) return e;
@@ -172,8 +174,9 @@ int lz4_precheck(const tyche_lz4_dict *, bool decode) {
 }
 int zstd_precheck(const tyche_lz4_dict *d, bool) { return zdict_structured(d) ? zdict_structured_error() : TYCHE_E_OK; }
 int zlib_precheck(const tyche_lz4_dict *, bool) { return TYCHE_E_OK; }   // raw bytes are raw bytes to zlib: every handle
-hipError_t lz4_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, const void *, bool per_page, hipStream_t s) {
-    return launch_lz4_encode_dict(b, in_cap, d, per_page, s);
+// (a seed was asked for: LZ4_HC_DICT was set when the launch read it, encode_seed)
+hipError_t lz4_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, const void *seed, bool per_page, hipStream_t s) {
+    return seed ? launch_lz4_encode_hc_dict(b, in_cap, d, seed, per_page, s) : launch_lz4_encode_dict(b, in_cap, d, per_page, s);
 }
 uint32_t lz4_stream_bound(uint32_t n) { return lz4_bound(n); }
 uint32_t zstd_stream_bound(uint32_t n) { return zstd_bound(n); }
@@ -186,7 +189,7 @@ struct tyche::DictCodec {
     bool (*refuses)(const tyche_lz4_dict *);                 // a handle this codec cannot take (NULL: takes every one)
     int (*precheck)(const tyche_lz4_dict *, bool decode);
     uint32_t (*bound)(uint32_t);
-    int seed;                   // the seeded table of the handle's that the encoder takes (kSeedNone: none)
+    int seed;                   // the seeded table of the handle's that the encoder takes (kSeedNone: none; encode_seed)
     hipError_t (*encode)(const tyche_batch_t &, uint32_t in_cap, const Lz4DictDev &, const void *seed, bool per_page, hipStream_t);
     hipError_t (*decode)(const tyche_batch_t &, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &, bool per_page, hipStream_t);
 };
@@ -201,6 +204,12 @@ const DictCodec &tyche::dict_codec(int compressor_id) {
 }
 
 namespace {
+// The seeded table an encode launch asks for, read once per launch: the codec's own, and for LZ4 the
+// HC rings when LZ4_HC_DICT is set (the knob chooses lz4_encode_dict's kernel through it) -- zstd and
+// zlib never read the knob.
+int encode_seed(const DictCodec &c) {
+    return &c == &dict_codec(kLz4) ? (knob("LZ4_HC_DICT", 0) != 0 ? kSeedLz4Hc : kSeedNone) : c.seed;
+}
 // TYCHE_LZ4_DICT_AUTO: the host compress calls collect sample pages (packed in `sample`, their
 // lengths in `sample_len`) until `pages` pages or TYCHE_LZ4_TRAIN_MAX_BYTES; the call that
 // completes the sample takes it away (kTraining) and trains outside the lock.  Only the LZ4 slot
@@ -331,7 +340,8 @@ int batch_dict(const DictCodec &c, bool decode, const tyche_lz4_dict *d, const t
     if (int rc = stream_device(s)) return rc;
     Lz4DictDev img;
     const void *seed = nullptr;
-    if (dict_on_device(d, &img, !decode && c.seed ? &seed : nullptr, c.seed) != hipSuccess) return TYCHE_E_DEVICE;
+    const int which = decode ? kSeedNone : encode_seed(c);
+    if (dict_on_device(d, &img, which ? &seed : nullptr, which) != hipSuccess) return TYCHE_E_DEVICE;
     hipError_t e;
     if (decode)
         // (a declared stream maximum is only a bound -- a slot width, say: above the longest stream a
@@ -377,7 +387,8 @@ hipError_t tyche::dict_launch(const DictCodec &c, bool decode, const tyche_lz4_d
                               const tyche_batch_t &b, hipStream_t s, bool host_dst, LaunchRef plain) {
     Lz4DictDev img;
     const void *seed = nullptr;
-    if (const hipError_t ue = note.upload(d, &img, !decode && c.seed ? &seed : nullptr, c.seed)) return ue;
+    const int which = decode ? kSeedNone : encode_seed(c);
+    if (const hipError_t ue = note.upload(d, &img, which ? &seed : nullptr, which)) return ue;
     const uint32_t reach = 65536u - d->len, longest = std::max(b.max_src_length, 1u);
     const uint32_t in_cap = decode ? std::min(b.max_src_length, c.bound(65536u)) : longest;   // (a stream bound, as batch_dict's)
     const uint32_t cap = decode ? b.dst_capacity : longest;

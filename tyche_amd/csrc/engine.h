@@ -141,6 +141,16 @@ hipError_t launch_lz4_encode_dict(const tyche_batch_t &b, uint32_t in_cap, const
                                   hipStream_t s);
 hipError_t launch_lz4_decode_dict(const tyche_batch_t &b, uint32_t in_cap, uint32_t out_cap, const Lz4DictDev &d,
                                   bool per_page, hipStream_t s);
+// LZ4_HC_DICT=1: the dictionary encoder's window and contract with LZ4_HC's parse -- 8-way bucket rings
+// that start from the handle's seed, lz4_hc_dict_seed_bytes() bytes that lz4_hc_dict_seed_table computes
+// on the host from the dictionary's last d.enc_len bytes (lz4_hc_dict_seed.hip; dict.hip builds and
+// uploads it at the handle's first such compress on a device), and a two-step lazy choice, one wave per
+// page (lz4_encode_hc_dict.hip).  The block is an ordinary dictionary block: launch_lz4_decode_dict
+// restores it.
+size_t lz4_hc_dict_seed_bytes();
+void lz4_hc_dict_seed_table(const uint8_t *tail, uint32_t n, void *table_out);
+hipError_t launch_lz4_encode_hc_dict(const tyche_batch_t &b, uint32_t in_cap, const Lz4DictDev &d, const void *seed,
+                                     bool per_page, hipStream_t s);
 // Trains a shared LZ4 dictionary of up to dict_len bytes (128 .. TYCHE_LZ4_DICT_MAX) from the batch's source
 // pages on stream s and waits for it (lz4_dict_train.hip; the dst fields are ignored).  dict_out: dict_len
 // host bytes.  hipSuccess with res->too_long (a page above in_cap <= 65535) or res->total_bytes above

@@ -26,7 +26,12 @@
 //     alone, no search): later pages of text match into them.
 // The stream is written as far as dst_capacity reaches, never beyond, and the
 // result is its size when all of it fitted, else 0.
-// Every loop carries a bound derived from L or the block, so a logic error ends
+// The dictionary encoder (lz4_encode_hc_dict.hip, LZ4_HC_DICT=1; host emulator
+// tools/lz4_hc_dict_emul.cpp) runs the same parse from a start position: the
+// dictionary's tail in front of the page is history that candidates may lie in,
+// and the rings start from a seed instead of from zero (seed_window,
+// encode_window).  The plain page is the window whose start is 0.
+// Every loop carries a bound derived from the window or the block, so a logic error ends
 // in a wrong answer, never in a wave that does not finish.
 //
 // The includer defines LZH_HOST (1: lanes are loops over arrays; 0: SIMT) and,
@@ -143,18 +148,32 @@ LZX_FN uint32_t probe(const uint8_t *in, uint32_t q, uint32_t c, uint32_t matchl
     return n;
 }
 
-// The page in[0, L) into dst[0, cap): the stream's size, or 0 when it does not
-// fit cap.  table: kTableEntries entries and cnt: kBuckets bytes, both zeroed
-// (an unwritten slot is candidate 0, verified like any other).  No byte past
-// in[L - 1] is read.
-LZX_FN int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, uint8_t *cnt, uint8_t *dst,
-                           uint32_t cap LZX_LANE_PARAM) {
+// The dictionary encoder's seed (lz4_encode_hc_dict.hip): what inserting the
+// positions 0 .. start - 4 of a window, those whose 4 bytes lie wholly in front
+// of start, leaves in a zeroed table and zeroed counters.  Reads in[0, start).
+LZX_FN void seed_window(const uint8_t *in, uint32_t start, uint16_t *table, uint8_t *cnt LZX_LANE_PARAM) {
+    if (start >= 4u) insert(in, start - 4u, table, cnt, 0u, start - 3u LZX_LANE_ARG);
+}
+
+// The page in[start, W) of the window in[0, W), W <= 65536, into dst[0, cap):
+// the stream's size, or 0 when it does not fit cap.  in[0, start) is history
+// (a dictionary): blocks, the anchor and so every backward catch-up begin at
+// start, candidates may be any earlier window position, and the end-of-block
+// rules hold on the page.  table: kTableEntries entries and cnt: kBuckets
+// bytes, as seed_window left them (start == 0: zeroed; an unwritten slot is
+// candidate 0, verified like any other); the three positions in front of start
+// whose 4 bytes run into the page are inserted here, so that a run across the
+// seam finds its source.  No byte past in[W - 1] is read.
+LZX_FN int32_t encode_window(const uint8_t *in, uint32_t start, uint32_t W, uint16_t *table, uint8_t *cnt, uint8_t *dst,
+                             uint32_t cap LZX_LANE_PARAM) {
     using lzx::ctz64;
-    const uint32_t mflimit = L - lzx::kMfLimitX, matchlimit = L - lzx::kLastLiteralsX;   // used when L >= 13
-    uint32_t anchor = 0, op = 0;
-    if (L >= lzx::kMinLength) {
-        uint32_t base = 0;
-        for (uint32_t it = 0; it <= L / kStride + 2u && base <= mflimit; it++) {
+    const uint32_t L = W;   // the writers' and the loops' bound
+    const uint32_t mflimit = W - lzx::kMfLimitX, matchlimit = W - lzx::kLastLiteralsX;   // used when W - start >= 13
+    uint32_t anchor = start, op = 0;
+    if (W - start >= lzx::kMinLength) {
+        if (start >= 3u) insert(in, mflimit, table, cnt, start - 3u, start LZX_LANE_ARG);
+        uint32_t base = start;
+        for (uint32_t it = 0; it <= (W - start) / kStride + 2u && base <= mflimit; it++) {
             LZX_V(uint32_t, q);
             LZX_V(uint32_t, w);
             LZX_V(uint32_t, h);
@@ -257,6 +276,13 @@ LZX_FN int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, uint8
         }
     }
     return (int32_t)(op + total);
+}
+
+// The page in[0, L) into dst[0, cap) from a zeroed table and zeroed counters
+// (LZ4_HC=1): a window without history.
+LZX_FN int32_t encode_page(const uint8_t *in, uint32_t L, uint16_t *table, uint8_t *cnt, uint8_t *dst,
+                           uint32_t cap LZX_LANE_PARAM) {
+    return encode_window(in, 0u, L, table, cnt, dst, cap LZX_LANE_ARG);
 }
 
 }  // namespace lzh
